@@ -15,6 +15,12 @@ max-over-ranks time and the final metric gather only.
 Configs (BASELINE.json): c2 (default, the headline line), c4 (SNR-aligned one-step path),
 c5 (30 s clips, N=200, fp32), and `--gpus 0` = c1 (the reference's CPU plumbing case, run by the
 CPU oracle: no GPU).  Prints ONE JSON line (rank 0).  See DESIGN.md §4 for the roofline definition.
+
+A plain run sets up, warms up, times `--steps` steps and prints the line (`roofline`, `cpu_baseline`, `parity`
+null).  `--full` adds what takes runs of its own after the timed region: the roofline probe pass, the parity
+check against the goldens, the fp32x3 parity-mode / bf16 format-cost legs beside the default C2 line and the CPU
+baseline (each still switched off by its --no-* option).  `--dump-outputs DIR` writes what the last timed step
+returned as DIR/<name>.npy (float32 / float64); the inputs and noise seeds depend on the arguments only.
 """
 from __future__ import annotations
 
@@ -83,6 +89,24 @@ def snrnet_formula(dev):
     net = SNRNet()
     net.load_state_dict(snrnet_formula_sd())
     return net
+
+
+DUMP_CAP = 64 << 20  # bytes --dump-outputs may write in all
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: {name: array} -> out_dir/<name>.npy, floating arrays as float32 (float64 kept), at most
+    DUMP_CAP bytes in all; an array over its share is stored as a fixed sample of its flattened elements
+    (sorted indices drawn without replacement by PCG64 seed 0, so two runs store the same elements)."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_CAP // max(len(arrays), 1)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+        if a.nbytes > share:
+            idx = np.sort(np.random.Generator(np.random.PCG64(0)).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 # ----------------------------------------------------------------------------- CPU baseline
@@ -316,12 +340,17 @@ def run_c1(args):
         for _ in range(args.steps):
             xh, t_hat = one_step()
         el = time.perf_counter() - t0
-        Y = torch.from_numpy(spec_ref.pad_spec(spec_ref.spec_fwd(spec_ref.stft(y / np.abs(y).max())))
-                             .astype(np.complex64))[:, None]
-        t1 = time.perf_counter()
-        xp, ns = sde_ref.pc_sample(sde_ref.OUVE(1.5, 0.05, 0.5, N=5), lambda x, t, Yc: -ncsnpp_ref.ncsnpp_forward(
-            torch.cat([x, Yc], 1), torch.full((1,), float(t)), sd), Y, noise, N=5)
-        t_pc = time.perf_counter() - t1
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"enhanced": np.asarray(xh).reshape(1, -1), "t_hat": np.array([t_hat], np.float64)})
+        plumbing = None
+        if args.full:  # one N=5 PC run as the plumbing check of the sampler path
+            Y = torch.from_numpy(spec_ref.pad_spec(spec_ref.spec_fwd(spec_ref.stft(y / np.abs(y).max())))
+                                 .astype(np.complex64))[:, None]
+            t1 = time.perf_counter()
+            xp, ns = sde_ref.pc_sample(sde_ref.OUVE(1.5, 0.05, 0.5, N=5), lambda x, t, Yc: -ncsnpp_ref.ncsnpp_forward(
+                torch.cat([x, Yc], 1), torch.full((1,), float(t)), sd), Y, noise, N=5)
+            t_pc = time.perf_counter() - t1
+            plumbing = {"nfe": ns, "seconds": t_pc, "finite": bool(torch.isfinite(torch.view_as_real(xp)).all())}
     value = args.steps / el
     cpu = {"value": value, "unit": "utt/s", "cores": env["cores"], "kind": "port",
            "sample": f"C1 itself: {args.steps} one-step enhancements of the 4 s VBD clip",
@@ -336,7 +365,7 @@ def run_c1(args):
                        "global_batch": 1, "per_gpu_batch": 1, "seq_len": 512, "parallelism": "none (CPU)"},
             "roofline": None, "cpu_baseline": cpu, "t_hat": float(t_hat),
             "output_rms": float(np.sqrt(np.mean(np.asarray(xh, np.float64) ** 2))),
-            "pc_n5_plumbing": {"nfe": ns, "seconds": t_pc, "finite": bool(torch.isfinite(torch.view_as_real(xp)).all())}}
+            "pc_n5_plumbing": plumbing}
     print(json.dumps(line), flush=True)
 
 
@@ -463,12 +492,20 @@ def run_train(args):
         loss = step(args.warmup + k)
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
-    probe.install(ops)
-    try:
-        step(999)
-    finally:
-        probe.uninstall()
-    by = probe.summary()
+    if args.dump_outputs:  # the last timed step's loss and the parameters it left (a fixed sample beyond the cap)
+        torch.cuda.synchronize()
+        out = {"loss": loss.detach().float().cpu().numpy().reshape(1)}
+        flat = torch.cat([p.detach().float().reshape(-1) for p in m.dnn.parameters()])
+        out["dnn_parameters"] = flat.cpu().numpy()
+        dump_outputs(args.dump_outputs, out)
+    by = None
+    if args.full:  # one more step under the conv probe
+        probe.install(ops)
+        try:
+            step(999)
+        finally:
+            probe.uninstall()
+        by = probe.summary()
     roof = None
     if by:
         kname = max(by, key=lambda k: by[k][1])
@@ -572,6 +609,8 @@ def run(args):
     rms = xh.pow(2).mean(dim=1).sqrt().double().cpu().tolist()
     allm = sdist.gather_metrics(rms, B * world, rank, world, dev)
     value = args.steps * B * world / elapsed
+    if args.dump_outputs:  # the last timed step's enhanced waveforms [B, L], one file per rank
+        dump_outputs(args.dump_outputs, {"enhanced" if world == 1 else f"enhanced_rank{rank}": xh.float().cpu().numpy()})
 
     roof = None
     if not args.no_probe:
@@ -778,6 +817,12 @@ def main():
     ap.add_argument("--dtype", choices=["fp16", "bf16", "fp32", "fp32x3"], default=None,
                     help="fp16 (c2 / c4 default); bf16 (the same kernels on bf16); fp32 (exact fp32 MFMA GEMMs); "
                          "fp32x3 (fp32 activations, split-bf16 GEMMs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need, after the timed steps: roofline probe pass, "
+                         "parity checks vs the goldens, the fp32x3 parity-mode and bf16 format-cost legs, CPU baseline "
+                         "(off by default; the --no-* options below switch single parts off under --full)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned as DIR/<name>.npy (float32 / float64, at most 64 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-probe", action="store_true")
     ap.add_argument("--no-parity-mode", action="store_true",
@@ -792,6 +837,10 @@ def main():
     ap.add_argument("--cpu-full", default=None, metavar="PATH",
                     help="only run the CPU baseline with one full N=30 utterance and write it to PATH")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:  # a plain run: set-up, warm-up, the timed steps, the line
+        args.no_cpu_baseline = args.no_probe = args.no_parity = args.no_parity_mode = True
     for k, v in CONFIG_DEFAULTS[args.config].items():
         if getattr(args, k) is None:
             setattr(args, k, v)

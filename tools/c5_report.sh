@@ -12,7 +12,7 @@ OUT=$ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 SNRSE_PROBE_DUMP=$OUT/probe_dump.json timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o run -- \
-  python3 "$ROOT/bench.py" --config c5 --N 2 --steps 1 --warmup 1 --no-cpu-baseline --no-parity > "$OUT/bench_traced.json" 2> "$OUT/bench_traced.err"
+  python3 "$ROOT/bench.py" --config c5 --N 2 --steps 1 --warmup 1 --full --no-cpu-baseline --no-parity > "$OUT/bench_traced.json" 2> "$OUT/bench_traced.err"
 python3 "$ROOT/tools/prof_summary.py" "$OUT/stats/run_kernel_stats.csv" "$OUT/kernel_stats.md" 3 > /dev/null
 python3 "$ROOT/tools/probe_reconcile.py" "$OUT/stats/run_kernel_trace.csv" "$OUT/bench_traced.json" "$OUT/probe_vs_rocprof.json" \
   "$OUT/probe_dump.json"

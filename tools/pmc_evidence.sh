@@ -19,7 +19,7 @@ for DT in bf16 fp32x3; do
   rm -rf "$OUT/${DT}_FETCH_SIZE" "$OUT/${DT}_WRITE_SIZE"
 done
 SNRSE_PROBE_DUMP=$OUT/x3_probe_dump.json timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d "$OUT/x3trace" -o run -- \
-  python3 "$ROOT/bench.py" --dtype fp32x3 --steps 1 --warmup 0 --N 2 --no-cpu-baseline --no-parity > "$OUT/x3_traced.json" 2> "$OUT/x3_traced.err"
+  python3 "$ROOT/bench.py" --dtype fp32x3 --steps 1 --warmup 0 --N 2 --full --no-cpu-baseline --no-parity > "$OUT/x3_traced.json" 2> "$OUT/x3_traced.err"
 python3 "$ROOT/tools/probe_reconcile.py" "$OUT/x3trace/run_kernel_trace.csv" "$OUT/x3_traced.json" "$OUT/x3_probe_vs_rocprof.json" "$OUT/x3_probe_dump.json"
 rm -rf "$OUT/x3trace"
 echo done > $OUT/DONE

@@ -13,7 +13,7 @@ mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 BARGS="$@"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o run -- \
-  python3 "$ROOT/bench.py" --steps 2 --warmup 1 --no-cpu-baseline $BARGS > "$OUT/bench_traced.json" 2> "$OUT/bench_traced.err"
+  python3 "$ROOT/bench.py" --steps 2 --warmup 1 --full --no-cpu-baseline $BARGS > "$OUT/bench_traced.json" 2> "$OUT/bench_traced.err"
 python3 "$ROOT/tools/prof_summary.py" "$OUT/trace/run_kernel_stats.csv" "$OUT/kernel_stats.md" 3 > /dev/null
 rm -f "$OUT/trace/run_kernel_trace.csv"
 timeout -s KILL 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/fetch" -o run -- \
