@@ -147,6 +147,13 @@ SNRSE_DEV float bfly_sum(float (&p)[N], int lane) {
   return v;
 }
 
+// XCD-aware bijective remap of block `bid` of `nblocks`: consecutive logical tiles share an XCD (its L2 holds the
+// halo rows and the weight tile they all re-read); N-tiles of one M-tile are adjacent.
+SNRSE_DEV int xcd_block_id(int bid, int nblocks) {
+  const int q8 = nblocks >> 3, r8 = nblocks & 7, xcd = bid & 7, pos = bid >> 3;
+  return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + pos;
+}
+
 SNRSE_DEV float dot4(const f32x4& a, const f32x4& b) {
   return fmaf(a[0], b[0], fmaf(a[1], b[1], fmaf(a[2], b[2], a[3] * b[3])));
 }

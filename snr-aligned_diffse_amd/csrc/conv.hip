@@ -27,19 +27,10 @@
 using namespace snrse_conv;
 
 namespace {
-
-
-// Shared epilogue: y = (acc + bias + temb + res) * out_scale + combine; optional GroupNorm
-// statistics of y (per (b, channel) sum / sumsq) for the consumer's GroupNorm.
+// Every epilogue below computes y = (acc + bias + temb + res) * out_scale + combine and, optionally, the
+// GroupNorm statistics of y (per (b, channel) sum / sumsq) for the consumer's GroupNorm.
 // acc[i][j][e]: row = mb + i*16 + (lane>>4)*4 + e, col = nb + j*16 + (lane&15).
-// LDS-staged epilogue for one wave's 64 x 64 tile (rows = 64 consecutive output pixels
-// mb.., cols = output channels nb..): the fp32 accumulators go to a per-wave LDS image,
-// then every lane finishes 8 rows x one 16-byte chunk of channels, so residual loads and
-// output stores are 16-B vectors and the GN statistics need one atomic pair per channel
-// per wave.  `stage` = this wave's 64 x 68 float region (caller barriers before reuse).
-// When the whole block tile lies in one image (blk_b >= 0) the GN statistics are reduced over
-// the block's NWM wave rows in LDS (`red`, NWM x BN x 2 floats) and leave as one atomic pair per
-// channel per block; every wave of the block must call this (it holds a barrier then).
+
 // Block-level GN statistics flush: sum the NWM wave rows of `red` and add one (sum, sumsq)
 // pair per channel to the slotted stats buffer.  Holds a barrier (all waves call it).
 template <int NWM, int BN>
@@ -56,6 +47,14 @@ SNRSE_DEV void block_stats_flush(const ConvParams& p, const float* red, int blk_
   }
 }
 
+// LDS-staged epilogue for one wave's 64 x 64 tile (rows = 64 consecutive output pixels
+// mb.., cols = output channels nb..): the fp32 accumulators go to a per-wave LDS image,
+// then every lane finishes 8 rows x one 16-byte chunk of channels, so residual loads and
+// output stores are 16-B vectors and the GN statistics need one atomic pair per channel
+// per wave.  `stage` = this wave's 64 x 68 float region (caller barriers before reuse).
+// When the whole block tile lies in one image (blk_b >= 0) the GN statistics are reduced over
+// the block's NWM wave rows in LDS (`red`, NWM x BN x 2 floats) and leave as one atomic pair per
+// channel per block; every wave of the block must call this (it holds a barrier then).
 // nvalid < 64: only the wave's first nvalid rows are output pixels (a tile cut by the image's right
 // edge, conv_x3h_kernel); the rest are skipped.
 template <typename TO, int NWM, int BN, bool DEFER = false, int LA = 8>
@@ -167,19 +166,7 @@ SNRSE_DEV void epilogue_lds(const ConvParams& p, const f32x4 (&acc)[4][4], int m
 #pragma unroll
       for (int k = 0; k < EPC; ++k) v[k] += tb[k];
     }
-    if (p.res) {
-      const u32x4 rv = rpre[pass];
-      if constexpr (sizeof(TO) == 2) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          v[2 * k] += H16<TO>::lo(rv[k]);
-          v[2 * k + 1] += H16<TO>::hi(rv[k]);
-        }
-      } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] += __uint_as_float(rv[k]);
-      }
-    }
+    if (p.res) epi_residual<TO>(rpre[pass], v);
 #pragma unroll
     for (int k = 0; k < EPC; ++k) v[k] *= p.out_scale;
     if (p.comb_src) {
@@ -187,14 +174,7 @@ SNRSE_DEV void epilogue_lds(const ConvParams& p, const f32x4 (&acc)[4][4], int m
 #pragma unroll
       for (int k = 0; k < EPC; ++k) v[k] += q[0] * cw[k][0] + q[1] * cw[k][1] + q[2] * cw[k][2] + q[3] * cw[k][3] + cb[k];
     }
-    u32x4 o;
-    if constexpr (sizeof(TO) == 2) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) o[k] = H16<TO>::pack(v[2 * k], v[2 * k + 1]);
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) o[k] = __float_as_uint(v[k]);
-    }
+    const u32x4 o = epi_pack<TO>(v);
     if (p.epi_nt)  // (the fp32x3 halo GEMM under option x3_nt; 0 on every other launch through here)
       __builtin_nontemporal_store(o, (u32x4*)((TO*)p.out + (size_t)m * p.out_ld + n));
     else
@@ -359,19 +339,7 @@ SNRSE_DEV void epilogue_img(const ConvParams& p, const f32x4 (&acc)[4][4], int m
     const float* sr = stage + row * LDR + cc * EPC;
 #pragma unroll
     for (int k = 0; k < EPC; ++k) v[k] = sr[k] + add[k];
-    if (f_res) {
-      const u32x4 rv = rpre[pass];
-      if constexpr (sizeof(TO) == 2) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          v[2 * k] += H16<TO>::lo(rv[k]);
-          v[2 * k + 1] += H16<TO>::hi(rv[k]);
-        }
-      } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] += __uint_as_float(rv[k]);
-      }
-    }
+    if (f_res) epi_residual<TO>(rpre[pass], v);
     if (p.out_scale != 1.f) {  // (uniform: Conv_0 and the other unscaled convs skip the multiply)
 #pragma unroll
       for (int k = 0; k < EPC; ++k) v[k] *= p.out_scale;
@@ -381,14 +349,7 @@ SNRSE_DEV void epilogue_img(const ConvParams& p, const f32x4 (&acc)[4][4], int m
 #pragma unroll
       for (int k = 0; k < EPC; ++k) v[k] += q[0] * cw[k][0] + q[1] * cw[k][1] + q[2] * cw[k][2] + q[3] * cw[k][3] + cb[k];
     }
-    u32x4 o;
-    if constexpr (sizeof(TO) == 2) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) o[k] = H16<TO>::pack(v[2 * k], v[2 * k + 1]);
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) o[k] = __float_as_uint(v[k]);
-    }
+    const u32x4 o = epi_pack<TO>(v);
     if (f_nt)  // option "epi_nt": streaming (non-temporal) output stores
       __builtin_nontemporal_store(o, (u32x4*)((TO*)p.out + m * p.out_ld + n));
     else
@@ -474,9 +435,96 @@ SNRSE_DEV void epilogue(const ConvParams& p, const f32x4 (&acc)[FM][FN], int mb,
   }
 }
 
-template <typename T, typename TO, int BM, int BN, int WM, int WN>
-__global__ __launch_bounds__(64 * WM * WN) void conv_mfma_kernel(ConvParams p) {
-  using Tr = ConvTraits<T>;
+// ---------------------------------------------------------------------------------------
+// The register-staged GEMM (v1): a BM x BN block tile of WM x WN waves; every K-tile's A rows (one pixel's 128 B of
+// one tap, zero outside the image) and B rows go global -> registers -> LDS, double buffered, one barrier per K-tile.
+// The operand policy `Opnd` supplies the K-tile size KT, the activation (A) and weight-row (W) element types, the
+// weight row factor WROW, stage_a (a thread's 16-B A vector -> LDS), mac (one K-tile's fragment reads + MFMAs) and
+// kLdsEpilogue (a 64 x 64 wave tile finishes through epilogue_lds; the caller's LDS must cover its staging).
+
+// 16-bit or f32 operands as they are: one MFMA chunk per K half
+template <typename T>
+struct PlainOpnd {
+  using A = T;
+  using W = T;
+  static constexpr int KT = ConvTraits<T>::KT, WROW = 1;
+  static constexpr bool kLdsEpilogue = false;  // (conv_mfma_kernel's LDS does not cover the staging)
+  SNRSE_DEV static void stage_a(char* as, int r, int ch, const u32x4& v) { *(u32x4*)(as + swz(r, ch)) = v; }
+  template <int FM, int FN>
+  SNRSE_DEV static void mac(const char* as, const char* bs, int arow, int brow, int lane, f32x4 (&acc)[FM][FN]) {
+    const int lrow = lane & 15, lg = lane >> 4;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      u32x4 af[FM], bfr[FN];
+#pragma unroll
+      for (int i = 0; i < FM; ++i) af[i] = *(const u32x4*)(as + swz(arow + i * 16 + lrow, 4 * s + lg));
+#pragma unroll
+      for (int j = 0; j < FN; ++j) bfr[j] = *(const u32x4*)(bs + swz(brow + j * 16 + lrow, 4 * s + lg));
+#pragma unroll
+      for (int i = 0; i < FM; ++i)
+#pragma unroll
+        for (int j = 0; j < FN; ++j) acc[i][j] = mfma_chunk<T>(af[i], bfr[j], acc[i][j]);
+    }
+  }
+};
+
+// Split-bf16 ("bf16x3") fp32 GEMM, the fast fp32 parity mode (dtype SNRSE_F32X3):
+// fp32 activations, weights pre-split on the host into hi = bf16(w), lo = bf16(w - hi), stored per
+// 32-element K-tile as one 128-B row [hi x 32 | lo x 32] ([Npad][2K] bf16).  The activation tile is
+// split the same way in registers on its way to LDS, and each K-tile accumulates
+//   A_hi B_hi + A_hi B_lo + A_lo B_hi
+// with three v_mfma_f32_16x16x32_bf16 (exact bf16 products, fp32 accumulation): the dropped lo*lo
+// term and the operands' residuals beyond 16 significant bits are ~2^-16 relative per product, and
+// one K-tile costs 48 MFMA cycles per 16x16 output block instead of the 256 of the eight
+// v_mfma_f32_16x16x4_f32 of the exact-fp32 form (measured: profiles/r03z_*).
+// LDS rows use the same swizzle, with the hi half in chunks 0-3 and the lo half in chunks 4-7.
+struct SplitBf16Opnd {
+  using A = float;
+  using W = bf16_t;
+  static constexpr int KT = 32, WROW = 2;
+  static constexpr bool kLdsEpilogue = true;
+  // 4 fp32 (elements 4ch .. 4ch+3 of the K-tile) -> 4 hi bf16 (8 B, hi half) + 4 lo bf16 (8 B, lo half)
+  SNRSE_DEV static void stage_a(char* as, int r, int ch, const u32x4& v) {
+    const uint32_t h01 = pack_bf16x2(__uint_as_float(v[0]), __uint_as_float(v[1]));
+    const uint32_t h23 = pack_bf16x2(__uint_as_float(v[2]), __uint_as_float(v[3]));
+    const uint32_t l01 = pack_bf16x2(__uint_as_float(v[0]) - __uint_as_float(h01 << 16),
+                                     __uint_as_float(v[1]) - __uint_as_float(h01 & 0xffff0000u));
+    const uint32_t l23 = pack_bf16x2(__uint_as_float(v[2]) - __uint_as_float(h23 << 16),
+                                     __uint_as_float(v[3]) - __uint_as_float(h23 & 0xffff0000u));
+    typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
+    *(u32x2*)(as + swz(r, ch >> 1) + (ch & 1) * 8) = u32x2{h01, h23};
+    *(u32x2*)(as + swz(r, 4 + (ch >> 1)) + (ch & 1) * 8) = u32x2{l01, l23};
+  }
+  template <int FM, int FN>
+  SNRSE_DEV static void mac(const char* as, const char* bs, int arow, int brow, int lane, f32x4 (&acc)[FM][FN]) {
+    const int lrow = lane & 15, lg = lane >> 4;
+    u32x4 ah[FM], al[FM], bh[FN], bl[FN];
+#pragma unroll
+    for (int i = 0; i < FM; ++i) {
+      ah[i] = *(const u32x4*)(as + swz(arow + i * 16 + lrow, lg));
+      al[i] = *(const u32x4*)(as + swz(arow + i * 16 + lrow, 4 + lg));
+    }
+#pragma unroll
+    for (int j = 0; j < FN; ++j) {
+      bh[j] = *(const u32x4*)(bs + swz(brow + j * 16 + lrow, lg));
+      bl[j] = *(const u32x4*)(bs + swz(brow + j * 16 + lrow, 4 + lg));
+    }
+#pragma unroll
+    for (int i = 0; i < FM; ++i)
+#pragma unroll
+      for (int j = 0; j < FN; ++j) {
+        acc[i][j] = mfma_chunk<bf16_t>(ah[i], bh[j], acc[i][j]);
+        acc[i][j] = mfma_chunk<bf16_t>(ah[i], bl[j], acc[i][j]);
+        acc[i][j] = mfma_chunk<bf16_t>(al[i], bh[j], acc[i][j]);
+      }
+  }
+};
+
+template <typename Opnd, typename TO, int BM, int BN, int WM, int WN>
+SNRSE_DEV void regstaged_gemm(const ConvParams& p, char* smem) {
+  using TA = typename Opnd::A;
+  using TW = typename Opnd::W;
+  constexpr int KT = Opnd::KT;
   constexpr int NT = 64 * WM * WN;
   constexpr int TM = BM / WM, TN = BN / WN;
   constexpr int FM = TM / 16, FN = TN / 16;
@@ -485,190 +533,17 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_mfma_kernel(ConvParams p) {
   constexpr int B_LD = (BN + ROWS_PER_PASS - 1) / ROWS_PER_PASS;
   static_assert(BM % 16 == 0 && BN % 16 == 0, "tile");
 
-  extern __shared__ __attribute__((aligned(16))) char smem[];
   // stage buffers: A[buf] at buf * BM * 128, B[buf] at 2 * BM * 128 + buf * BN * 128
-#define AS(buf) (smem + (buf) * (BM * 128))
-#define BS(buf) (smem + 2 * BM * 128 + (buf) * (BN * 128))
+  auto a_stage = [&](int buf) { return smem + buf * (BM * 128); };
+  auto b_stage = [&](int buf) { return smem + 2 * BM * 128 + buf * (BN * 128); };
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wid = tid >> 6;
   const int wm = wid / WN, wn = wid % WN;
-  const int nbk = gridDim.x, bid = blockIdx.x;
-  const int q8 = nbk >> 3, r8 = nbk & 7, xcd = bid & 7, pos = bid >> 3;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + pos;
+  const int wg = xcd_block_id(blockIdx.x, gridDim.x);
   // split-K (the small low-resolution levels of the fp32 path): the p.ksplit K ranges of one output
   // tile are adjacent logical ids, i.e. on one XCD
-  const int ks = wg % p.ksplit, tl = wg / p.ksplit;
-  const int m0 = (tl / p.ntn) * BM;
-  const int n0 = (tl % p.ntn) * BN;
-  const int HW = p.H * p.W;
-  const int Cin = p.C0 + p.C1;
-  const int cblocks = Cin / Tr::KT;
-  const int nk0 = p.ksize * p.ksize * cblocks;
-  const int Csc_all = p.Csc + p.Csc1;
-  const int nk = nk0 + (p.sc_src ? Csc_all / Tr::KT : 0);
-  const int K1 = p.ksize * p.ksize * Cin;
-  const int half = p.ksize >> 1;
-
-  const int ch = tid & 7;
-  // per-thread A rows: pixel coordinates
-  int a_b[A_LD], a_h[A_LD], a_w[A_LD];
-  bool a_ok[A_LD];
-#pragma unroll
-  for (int i = 0; i < A_LD; ++i) {
-    const int r = (tid >> 3) + i * ROWS_PER_PASS;
-    const int m = m0 + r;
-    a_ok[i] = (r < BM) && (m < p.M);
-    const int mm = a_ok[i] ? m : 0;
-    a_b[i] = mm / HW;
-    const int rem = mm - a_b[i] * HW;
-    a_h[i] = rem / p.W;
-    a_w[i] = rem - a_h[i] * p.W;
-  }
-
-  u32x4 ra[A_LD], rb[B_LD];
-
-  auto gload = [&](int kt) {
-    const T* src;
-    int cs, cc, dy, dx;
-    const T* wbase;
-    int wld;
-    if (kt < nk0) {
-      const int tap = kt / cblocks;
-      const int c = (kt - tap * cblocks) * Tr::KT;
-      dy = tap / p.ksize - half;
-      dx = tap % p.ksize - half;
-      if (c < p.C0) { src = (const T*)p.src0; cs = p.C0; cc = c; }
-      else { src = (const T*)p.src1; cs = p.C1; cc = c - p.C0; }
-      wbase = (const T*)p.wgt + tap * Cin + c;
-      wld = K1;
-    } else {
-      const int c = (kt - nk0) * Tr::KT;
-      if (c < p.Csc) { src = (const T*)p.sc_src; cs = p.Csc; cc = c; }
-      else { src = (const T*)p.sc_src1; cs = p.Csc1; cc = c - p.Csc; }
-      dy = 0; dx = 0;
-      wbase = (const T*)p.sc_wgt + c;
-      wld = Csc_all;
-    }
-#pragma unroll
-    for (int i = 0; i < A_LD; ++i) {
-      const int hh = a_h[i] + dy, ww = a_w[i] + dx;
-      const bool ok = a_ok[i] && hh >= 0 && hh < p.H && ww >= 0 && ww < p.W;
-      if (ok) {
-        const T* ptr = src + ((size_t)(a_b[i] * p.H + hh) * p.W + ww) * cs + cc + ch * Tr::EPC;
-        ra[i] = *(const u32x4*)ptr;
-      } else {
-        ra[i] = u32x4{0u, 0u, 0u, 0u};
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < B_LD; ++i) {
-      const int r = (tid >> 3) + i * ROWS_PER_PASS;
-      if (r < BN) {
-        const T* ptr = wbase + (size_t)(n0 + r) * wld + ch * Tr::EPC;
-        rb[i] = *(const u32x4*)ptr;
-      }
-    }
-  };
-  auto lstore = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < A_LD; ++i) {
-      const int r = (tid >> 3) + i * ROWS_PER_PASS;
-      if (r < BM) *(u32x4*)(AS(buf) + swz(r, ch)) = ra[i];
-    }
-#pragma unroll
-    for (int i = 0; i < B_LD; ++i) {
-      const int r = (tid >> 3) + i * ROWS_PER_PASS;
-      if (r < BN) *(u32x4*)(BS(buf) + swz(r, ch)) = rb[i];
-    }
-  };
-
-  f32x4 acc[FM][FN];
-#pragma unroll
-  for (int i = 0; i < FM; ++i)
-#pragma unroll
-    for (int j = 0; j < FN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  const int kb = (int)((long long)ks * nk / p.ksplit), ke = (int)((long long)(ks + 1) * nk / p.ksplit);
-  gload(kb);
-  lstore(0);
-  __syncthreads();
-
-  const int lrow = lane & 15;
-  const int lg = lane >> 4;
-  for (int kt = kb; kt < ke; ++kt) {
-    const int cur = (kt - kb) & 1;
-    if (kt + 1 < ke) gload(kt + 1);
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      u32x4 af[FM], bfr[FN];
-#pragma unroll
-      for (int i = 0; i < FM; ++i) af[i] = *(const u32x4*)(AS(cur) + swz(wm * TM + i * 16 + lrow, 4 * s + lg));
-#pragma unroll
-      for (int j = 0; j < FN; ++j) bfr[j] = *(const u32x4*)(BS(cur) + swz(wn * TN + j * 16 + lrow, 4 * s + lg));
-#pragma unroll
-      for (int i = 0; i < FM; ++i)
-#pragma unroll
-        for (int j = 0; j < FN; ++j) acc[i][j] = mfma_chunk<T>(af[i], bfr[j], acc[i][j]);
-    }
-    if (kt + 1 < ke) lstore(cur ^ 1);
-    __syncthreads();
-  }
-
-#undef AS
-#undef BS
-  if (p.ksplit > 1) {  // raw fp32 partial sums of this K range; conv_splitk_finalize applies the epilogue
-    float* const wsp = p.ws + (size_t)ks * p.M * p.Cout;
-#pragma unroll
-    for (int i = 0; i < FM; ++i)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int m = m0 + wm * TM + i * 16 + lg * 4 + e;
-        if (m < p.M) {
-#pragma unroll
-          for (int j = 0; j < FN; ++j) wsp[(size_t)m * p.Cout + n0 + wn * TN + j * 16 + lrow] = acc[i][j][e];
-        }
-      }
-    return;
-  }
-  epilogue<TO, FM, FN>(p, acc, m0 + wm * TM, n0 + wn * TN, lane);
-}
-
-// ---------------------------------------------------------------------------------------
-// Split-bf16 ("bf16x3") fp32 GEMM, the fast fp32 parity mode (dtype SNRSE_F32 with bf16 weights):
-// fp32 activations, weights pre-split on the host into hi = bf16(w), lo = bf16(w - hi), stored per
-// 32-element K-tile as one 128-B row [hi x 32 | lo x 32] ([Npad][2K] bf16).  The activation tile is
-// split the same way in registers on its way to LDS, and each K-tile accumulates
-//   A_hi B_hi + A_hi B_lo + A_lo B_hi
-// with three v_mfma_f32_16x16x32_bf16 (exact bf16 products, fp32 accumulation): the dropped lo*lo
-// term and the operands' residuals beyond 16 significant bits are ~2^-16 relative per product, and
-// one K-tile costs 48 MFMA cycles per 16x16 output block instead of the 256 of the eight
-// v_mfma_f32_16x16x4_f32 of the exact-fp32 kernel (measured: profiles/r03z_*).
-// Same tile walk, split-K and epilogues as the v1 kernel above; LDS rows use the same swizzle, with
-// the hi half in chunks 0-3 and the lo half in chunks 4-7.
-template <int BM, int BN, int WM, int WN>
-__global__ __launch_bounds__(64 * WM * WN) void conv_x3_kernel(ConvParams p) {
-  constexpr int KT = 32;  // fp32 elements per K-tile
-  constexpr int NT = 64 * WM * WN;
-  constexpr int TM = BM / WM, TN = BN / WN;
-  constexpr int FM = TM / 16, FN = TN / 16;
-  constexpr int ROWS_PER_PASS = NT / 8;
-  constexpr int A_LD = (BM + ROWS_PER_PASS - 1) / ROWS_PER_PASS;
-  constexpr int B_LD = (BN + ROWS_PER_PASS - 1) / ROWS_PER_PASS;
-  static_assert(BM % 16 == 0 && BN % 16 == 0, "tile");
-
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-#define AS(buf) (smem + (buf) * (BM * 128))
-#define BS(buf) (smem + 2 * BM * 128 + (buf) * (BN * 128))
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wid = tid >> 6;
-  const int wm = wid / WN, wn = wid % WN;
-  const int nbk = gridDim.x, bid = blockIdx.x;
-  const int q8 = nbk >> 3, r8 = nbk & 7, xcd = bid & 7, pos = bid >> 3;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + pos;
   const int ks = wg % p.ksplit, tl = wg / p.ksplit;
   const int m0 = (tl / p.ntn) * BM;
   const int n0 = (tl % p.ntn) * BN;
@@ -681,79 +556,74 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_x3_kernel(ConvParams p) {
   const int K1 = p.ksize * p.ksize * Cin;
   const int half = p.ksize >> 1;
 
-  const int ch = tid & 7;  // A: fp32 elements 4ch..4ch+3 of the K-tile; B: 16-B chunk ch of the split row
-  int a_b[A_LD], a_h[A_LD], a_w[A_LD];
+  const int ch = tid & 7;  // this thread's 16-B chunk of its A and B rows
+  // per-thread A rows: pixels pix0 + i * ROWS_PER_PASS and their image coordinates (a tap moves a pixel by
+  // dy * W + dx inside its image)
+  const int pix0 = m0 + (tid >> 3);
+  int a_h[A_LD], a_w[A_LD];
   bool a_ok[A_LD];
 #pragma unroll
   for (int i = 0; i < A_LD; ++i) {
     const int r = (tid >> 3) + i * ROWS_PER_PASS;
     const int m = m0 + r;
     a_ok[i] = (r < BM) && (m < p.M);
-    const int mm = a_ok[i] ? m : 0;
-    a_b[i] = mm / HW;
-    const int rem = mm - a_b[i] * HW;
+    const int rem = (a_ok[i] ? m : 0) % HW;
     a_h[i] = rem / p.W;
     a_w[i] = rem - a_h[i] * p.W;
   }
 
   u32x4 ra[A_LD], rb[B_LD];
+
+  // K-tile kt -> (source, channel offset, tap shift, weight rows) and the loads of this thread's A and B vectors
   auto gload = [&](int kt) {
-    const float* src;
+    const TA* src;
     int cs, cc, dy, dx;
-    const bf16_t* wbase;
+    const TW* wbase;
     int wld;
     if (kt < nk0) {
       const int tap = kt / cblocks;
       const int c = (kt - tap * cblocks) * KT;
       dy = tap / p.ksize - half;
       dx = tap % p.ksize - half;
-      if (c < p.C0) { src = (const float*)p.src0; cs = p.C0; cc = c; }
-      else { src = (const float*)p.src1; cs = p.C1; cc = c - p.C0; }
-      wbase = (const bf16_t*)p.wgt + 2 * (tap * Cin + c);
-      wld = 2 * K1;
+      if (c < p.C0) { src = (const TA*)p.src0; cs = p.C0; cc = c; }
+      else { src = (const TA*)p.src1; cs = p.C1; cc = c - p.C0; }
+      wbase = (const TW*)p.wgt + Opnd::WROW * (tap * Cin + c);
+      wld = Opnd::WROW * K1;
     } else {
       const int c = (kt - nk0) * KT;
-      if (c < p.Csc) { src = (const float*)p.sc_src; cs = p.Csc; cc = c; }
-      else { src = (const float*)p.sc_src1; cs = p.Csc1; cc = c - p.Csc; }
+      if (c < p.Csc) { src = (const TA*)p.sc_src; cs = p.Csc; cc = c; }
+      else { src = (const TA*)p.sc_src1; cs = p.Csc1; cc = c - p.Csc; }
       dy = 0; dx = 0;
-      wbase = (const bf16_t*)p.sc_wgt + 2 * c;
-      wld = 2 * Csc_all;
+      wbase = (const TW*)p.sc_wgt + Opnd::WROW * c;
+      wld = Opnd::WROW * Csc_all;
     }
 #pragma unroll
     for (int i = 0; i < A_LD; ++i) {
       const int hh = a_h[i] + dy, ww = a_w[i] + dx;
       const bool ok = a_ok[i] && hh >= 0 && hh < p.H && ww >= 0 && ww < p.W;
-      if (ok) ra[i] = *(const u32x4*)(src + ((size_t)(a_b[i] * p.H + hh) * p.W + ww) * cs + cc + ch * 4);
-      else ra[i] = u32x4{0u, 0u, 0u, 0u};
-    }
-#pragma unroll
-    for (int i = 0; i < B_LD; ++i) {
-      const int r = (tid >> 3) + i * ROWS_PER_PASS;
-      if (r < BN) rb[i] = *(const u32x4*)(wbase + (size_t)(n0 + r) * wld + ch * 8);
-    }
-  };
-  // A: 4 fp32 -> 4 hi bf16 (8 B, hi half) + 4 lo bf16 (8 B, lo half); B: the pre-split chunk as is
-  auto lstore = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < A_LD; ++i) {
-      const int r = (tid >> 3) + i * ROWS_PER_PASS;
-      if (r < BM) {
-        const u32x4 v = ra[i];
-        const uint32_t h01 = pack_bf16x2(__uint_as_float(v[0]), __uint_as_float(v[1]));
-        const uint32_t h23 = pack_bf16x2(__uint_as_float(v[2]), __uint_as_float(v[3]));
-        const uint32_t l01 = pack_bf16x2(__uint_as_float(v[0]) - __uint_as_float(h01 << 16),
-                                         __uint_as_float(v[1]) - __uint_as_float(h01 & 0xffff0000u));
-        const uint32_t l23 = pack_bf16x2(__uint_as_float(v[2]) - __uint_as_float(h23 << 16),
-                                         __uint_as_float(v[3]) - __uint_as_float(h23 & 0xffff0000u));
-        typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-        *(u32x2*)(AS(buf) + swz(r, ch >> 1) + (ch & 1) * 8) = u32x2{h01, h23};
-        *(u32x2*)(AS(buf) + swz(r, 4 + (ch >> 1)) + (ch & 1) * 8) = u32x2{l01, l23};
+      if (ok) {
+        const TA* ptr = src + (size_t)(pix0 + i * ROWS_PER_PASS + dy * p.W + dx) * cs + cc + ch * (16 / (int)sizeof(TA));
+        ra[i] = *(const u32x4*)ptr;
+      } else {
+        ra[i] = u32x4{0u, 0u, 0u, 0u};
       }
     }
 #pragma unroll
     for (int i = 0; i < B_LD; ++i) {
       const int r = (tid >> 3) + i * ROWS_PER_PASS;
-      if (r < BN) *(u32x4*)(BS(buf) + swz(r, ch)) = rb[i];
+      if (r < BN) rb[i] = *(const u32x4*)(wbase + (size_t)(n0 + r) * wld + ch * (16 / (int)sizeof(TW)));
+    }
+  };
+  auto lstore = [&](int buf) {
+#pragma unroll
+    for (int i = 0; i < A_LD; ++i) {
+      const int r = (tid >> 3) + i * ROWS_PER_PASS;
+      if (r < BM) Opnd::stage_a(a_stage(buf), r, ch, ra[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < B_LD; ++i) {
+      const int r = (tid >> 3) + i * ROWS_PER_PASS;
+      if (r < BN) *(u32x4*)(b_stage(buf) + swz(r, ch)) = rb[i];
     }
   };
 
@@ -768,57 +638,38 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_x3_kernel(ConvParams p) {
   lstore(0);
   __syncthreads();
 
-  const int lrow = lane & 15;
-  const int lg = lane >> 4;
   for (int kt = kb; kt < ke; ++kt) {
     const int cur = (kt - kb) & 1;
     if (kt + 1 < ke) gload(kt + 1);
-    u32x4 ah[FM], al[FM], bh[FN], bl[FN];
-#pragma unroll
-    for (int i = 0; i < FM; ++i) {
-      ah[i] = *(const u32x4*)(AS(cur) + swz(wm * TM + i * 16 + lrow, lg));
-      al[i] = *(const u32x4*)(AS(cur) + swz(wm * TM + i * 16 + lrow, 4 + lg));
-    }
-#pragma unroll
-    for (int j = 0; j < FN; ++j) {
-      bh[j] = *(const u32x4*)(BS(cur) + swz(wn * TN + j * 16 + lrow, lg));
-      bl[j] = *(const u32x4*)(BS(cur) + swz(wn * TN + j * 16 + lrow, 4 + lg));
-    }
-#pragma unroll
-    for (int i = 0; i < FM; ++i)
-#pragma unroll
-      for (int j = 0; j < FN; ++j) {
-        acc[i][j] = mfma_chunk<bf16_t>(ah[i], bh[j], acc[i][j]);
-        acc[i][j] = mfma_chunk<bf16_t>(ah[i], bl[j], acc[i][j]);
-        acc[i][j] = mfma_chunk<bf16_t>(al[i], bh[j], acc[i][j]);
-      }
+    Opnd::template mac<FM, FN>(a_stage(cur), b_stage(cur), wm * TM, wn * TN, lane, acc);
     if (kt + 1 < ke) lstore(cur ^ 1);
     __syncthreads();
   }
-#undef AS
-#undef BS
+
   if (p.ksplit > 1) {
-    float* const wsp = p.ws + (size_t)ks * p.M * p.Cout;
-#pragma unroll
-    for (int i = 0; i < FM; ++i)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int m = m0 + wm * TM + i * 16 + lg * 4 + e;
-        if (m < p.M) {
-#pragma unroll
-          for (int j = 0; j < FN; ++j) wsp[(size_t)m * p.Cout + n0 + wn * TN + j * 16 + lrow] = acc[i][j][e];
-        }
-      }
+    store_splitk_partials<FM, FN>(p, acc, ks, m0 + wm * TM, n0 + wn * TN, lane);
     return;
   }
-  if constexpr (TM == 64 && TN == 64) {
+  if constexpr (Opnd::kLdsEpilogue && TM == 64 && TN == 64) {
     // LDS-staged epilogue: 16-B output stores, one statistics atomic pair per channel per block
     const int b_lo = m0 / HW, b_hi = (min(m0 + BM, p.M) - 1) / HW;
-    epilogue_lds<float, WM, BN, false, 4>(p, acc, m0 + wm * TM, n0 + wn * TN, lane, (float*)(smem + wid * (64 * 68 * 4)),
-                                (float*)(smem + WM * WN * (64 * 68 * 4)), wm, b_lo == b_hi ? b_lo : -1, n0);
+    epilogue_lds<TO, WM, BN, false, 4>(p, acc, m0 + wm * TM, n0 + wn * TN, lane, (float*)(smem + wid * (64 * 68 * 4)),
+                                       (float*)(smem + WM * WN * (64 * 68 * 4)), wm, b_lo == b_hi ? b_lo : -1, n0);
   } else {
-    epilogue<float, FM, FN>(p, acc, m0 + wm * TM, n0 + wn * TN, lane);
+    epilogue<TO, FM, FN>(p, acc, m0 + wm * TM, n0 + wn * TN, lane);
   }
+}
+
+template <typename T, typename TO, int BM, int BN, int WM, int WN>
+__global__ __launch_bounds__(64 * WM * WN) void conv_mfma_kernel(ConvParams p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  regstaged_gemm<PlainOpnd<T>, TO, BM, BN, WM, WN>(p, smem);
+}
+
+template <int BM, int BN, int WM, int WN>
+__global__ __launch_bounds__(64 * WM * WN) void conv_x3_kernel(ConvParams p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  regstaged_gemm<SplitBf16Opnd, float, BM, BN, WM, WN>(p, smem);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -883,9 +734,7 @@ __global__ __launch_bounds__(512) void conv_x3h_kernel(ConvParams p) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wid & 3, wc = wid >> 2;
-  const int nb = gridDim.x, bid = blockIdx.x;
-  const int q8 = nb >> 3, r8 = nb & 7, xcd = bid & 7, pos = bid >> 3;
-  const int g = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + pos;
+  const int g = xcd_block_id(blockIdx.x, gridDim.x);
   const int n0 = (g % p.ntn) * 128;
   int tile = g / p.ntn;
   const int ntw = (p.W + TW - 1) / TW, nth = p.H / TH;  // the last tile column may be cut by the image edge
@@ -1291,11 +1140,7 @@ __global__ __launch_bounds__(512) void conv_glds_kernel(ConvParams p) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wid / WN, wn = wid % WN;
-  // XCD-aware bijective remap: consecutive logical tiles share an XCD (its L2 holds the halo
-  // rows and the weight tile they all re-read); N-tiles of one M-tile are adjacent.
-  const int nb = gridDim.x, bid = blockIdx.x;
-  const int q8 = nb >> 3, r8 = nb & 7, xcd = bid & 7, pos = bid >> 3;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + pos;
+  const int wg = xcd_block_id(blockIdx.x, gridDim.x);
   // split-K: the p.ksplit K ranges of one output tile are adjacent logical ids (same XCD)
   const int ks = wg % p.ksplit, tl = wg / p.ksplit;
   const int m0 = (tl / p.ntn) * BM;
@@ -1504,14 +1349,9 @@ __global__ __launch_bounds__(256) void conv_splitk_finalize(ConvParams p, int pp
       v[k] = a0[k] + add[k];
       v[4 + k] = a1[k] + add[4 + k];
     }
-    if (p.res) {
+    if (p.res) {  // (the 8 channels are one 16-B chunk of a 16-bit output only)
       if constexpr (sizeof(TO) == 2) {
-        const u32x4 rv = *(const u32x4*)((const TO*)p.res + m * p.res_ld + n);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          v[2 * k] += H16<TO>::lo(rv[k]);
-          v[2 * k + 1] += H16<TO>::hi(rv[k]);
-        }
+        epi_residual<TO>(*(const u32x4*)((const TO*)p.res + m * p.res_ld + n), v);
       } else {
         const float* rp = (const float*)p.res + m * p.res_ld + n;
 #pragma unroll
@@ -1526,10 +1366,7 @@ __global__ __launch_bounds__(256) void conv_splitk_finalize(ConvParams p, int pp
       for (int k = 0; k < 8; ++k) v[k] += q[0] * cw[k][0] + q[1] * cw[k][1] + q[2] * cw[k][2] + q[3] * cw[k][3] + cb[k];
     }
     if constexpr (sizeof(TO) == 2) {
-      u32x4 o;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) o[k] = H16<TO>::pack(v[2 * k], v[2 * k + 1]);
-      *(u32x4*)((TO*)p.out + m * p.out_ld + n) = o;
+      *(u32x4*)((TO*)p.out + m * p.out_ld + n) = epi_pack<TO>(v);
     } else {
       float* op = (float*)p.out + m * p.out_ld + n;
 #pragma unroll
@@ -1605,10 +1442,7 @@ __global__ __launch_bounds__(256, 2) void conv_halo5_kernel(ConvParams p) {
   unsigned long long* const lst = (unsigned long long*)(smem + kStampOff) + wid * 32;
 #endif
   SNRSE_STAMP(0);
-  const int nb = gridDim.x, bid = blockIdx.x;
-  const int q8 = nb >> 3, r8 = nb & 7, xcd = bid & 7, pos = bid >> 3;
-  const int g = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + pos;
-  const int wg = g;
+  const int wg = xcd_block_id(blockIdx.x, gridDim.x);
   const int n0 = (wg % p.ntn) * 128;
   int tile = wg / p.ntn;
   const int ntw = p.W / TW, nth = p.H / TH;
@@ -1950,6 +1784,39 @@ __global__ __launch_bounds__(256, 2) void conv_halo5_kernel(ConvParams p) {
 #endif
 }
 
+// ---------------------------------------------------------------------------------------------
+// Launch helpers
+
+// Launch kernel K with `lds` bytes of dynamic LDS, its limit raised first: once per kernel instantiation (a
+// function-local static, so the one-time set is thread-safe)
+template <auto K, typename... Args>
+int launch_dyn_lds(dim3 grid, dim3 block, size_t lds, hipStream_t s, const Args&... args) {
+  static const hipError_t attr = hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  SNRSE_RET(attr);
+  hipLaunchKernelGGL(K, grid, block, lds, s, args...);
+  return (int)hipGetLastError();
+}
+
+// the split-K finalize of a launch that left p.ksplit planes of partial sums in p.ws
+template <typename TO>
+int launch_splitk_finalize(const ConvParams& p, hipStream_t s) {
+  const int HW = p.H * p.W, ppb = 64;
+  hipLaunchKernelGGL((conv_splitk_finalize<TO>), dim3(p.B * ((HW + ppb - 1) / ppb), p.Cout / 128), dim3(256), 0, s, p,
+                     ppb);
+  return (int)hipGetLastError();
+}
+
+// K-tiles of KT channels of a launch: the taps of the (concatenated) input + the fused shortcut
+inline int k_tiles(const ConvParams& p, int KT) {
+  return p.ksize * p.ksize * ((p.C0 + p.C1) / KT) + (p.sc_src ? (p.Csc + p.Csc1) / KT : 0);
+}
+
+// non-temporal output stores (option epi_nt: 0 off, 1 on, 2 when the output exceeds the Infinity Cache, epi_nt_mb:
+// +1 % on the full-resolution convs)
+inline int stream_output(const snrse_ctx& cx, long long bytes) {
+  return cx.epi_nt == 2 ? bytes > ((long long)cx.epi_nt_mb << 20) : cx.epi_nt;
+}
+
 template <typename T, typename TO, int GNM, int EF, int TW, bool SCD>
 int launch_halo5_ef(ConvParams p, int grid, hipStream_t s) {
   // halo + weight ring + (stamps build: 4 x 32 stamps) + the next chunk's GroupNorm affine (2 x 32 f32),
@@ -1961,20 +1828,13 @@ int launch_halo5_ef(ConvParams p, int grid, hipStream_t s) {
 #else
   constexpr size_t lds = main_lds > epi_lds ? main_lds : epi_lds;
 #endif
-  static const hipError_t attr = hipFuncSetAttribute((const void*)conv_halo5_kernel<T, TO, GNM, EF, TW, SCD>,
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  SNRSE_RET(attr);  // (thread-safe one-time set: a function-local static)
-  hipLaunchKernelGGL((conv_halo5_kernel<T, TO, GNM, EF, TW, SCD>), dim3(grid), dim3(256), lds, s, p);
-  return (int)hipGetLastError();
+  return launch_dyn_lds<conv_halo5_kernel<T, TO, GNM, EF, TW, SCD>>(dim3(grid), dim3(256), lds, s, p);
 }
 
 template <typename T, typename TO, int GNM, int TW>
 int launch_halo5_gn(ConvParams p, hipStream_t s, snrse_ctx& cx) {
   p.ntn = p.Cout / 128;
-  // non-temporal output stores when the output exceeds the 256 MB Infinity Cache (+1 % on the
-  // full-resolution convs)
-  p.epi_nt = cx.epi_nt == 2 ? ((long long)p.M * p.out_ld * (long long)sizeof(TO) > ((long long)cx.epi_nt_mb << 20))
-                            : cx.epi_nt;
+  p.epi_nt = stream_output(cx, (long long)p.M * p.out_ld * (long long)sizeof(TO));
   cx.last_epi_nt = p.epi_nt;
   const int tiles = p.B * (p.H / (256 / TW)) * (p.W / TW) * p.ntn;
   const int grid = tiles;
@@ -2051,22 +1911,17 @@ int choose_ksplit(const ConvParams& p, int tiles, int nk, const snrse_ctx& cx, i
 // across workgroups (>= 2 K-tiles each) and finish in conv_splitk_finalize.
 template <typename T, typename TO, int BM, int BN, int WM, int WN>
 int launch_conv(ConvParams p, int npad, hipStream_t s, snrse_ctx& cx) {
-  using Tr = ConvTraits<T>;
   p.ntn = npad / BN;
   const int tiles = ((p.M + BM - 1) / BM) * p.ntn;
-  const int nk = p.ksize * p.ksize * ((p.C0 + p.C1) / Tr::KT) + (p.sc_src ? (p.Csc + p.Csc1) / Tr::KT : 0);
-  p.ksplit = (sizeof(T) == 4 && BN == 128 && p.Cout % 128 == 0) ? choose_ksplit(p, tiles, nk, cx, 2) : 1;
+  p.ksplit = (sizeof(T) == 4 && BN == 128 && p.Cout % 128 == 0)
+                 ? choose_ksplit(p, tiles, k_tiles(p, ConvTraits<T>::KT), cx, 2) : 1;
   p.ws = cx.ws;
   cx.last_ksplit = p.ksplit;
   const size_t lds = (size_t)2 * (BM + BN) * 128;
   hipLaunchKernelGGL((conv_mfma_kernel<T, TO, BM, BN, WM, WN>), dim3(tiles * p.ksplit), dim3(64 * WM * WN), lds, s, p);
-  if (p.ksplit > 1) {
-    SNRSE_LAUNCH_CHECK();
-    const int HW = p.H * p.W, ppb = 64;
-    hipLaunchKernelGGL((conv_splitk_finalize<TO>), dim3(p.B * ((HW + ppb - 1) / ppb), p.Cout / 128), dim3(256), 0, s,
-                       p, ppb);
-  }
-  return (int)hipGetLastError();
+  if (p.ksplit == 1) return (int)hipGetLastError();
+  SNRSE_LAUNCH_CHECK();
+  return launch_splitk_finalize<TO>(p, s);
 }
 
 template <int BM, int BN, int WM, int WN>
@@ -2074,36 +1929,22 @@ int launch_x3(ConvParams p, hipStream_t s, snrse_ctx& cx) {
   constexpr size_t main_lds = (size_t)2 * (BM + BN) * 128;
   constexpr size_t epi_lds = (BM / WM == 64 && BN / WN == 64) ? (size_t)WM * WN * 64 * 68 * 4 + WM * BN * 2 * 4 : 0;
   constexpr size_t lds = main_lds > epi_lds ? main_lds : epi_lds;
-  static const hipError_t attr = hipFuncSetAttribute((const void*)conv_x3_kernel<BM, BN, WM, WN>,
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  SNRSE_RET(attr);
   p.ntn = (p.Cout + BN - 1) / BN;
   const int tiles = ((p.M + BM - 1) / BM) * p.ntn;
-  const int nk = p.ksize * p.ksize * ((p.C0 + p.C1) / 32) + (p.sc_src ? (p.Csc + p.Csc1) / 32 : 0);
-  p.ksplit = BN == 128 ? choose_ksplit(p, tiles, nk, cx, 2) : 1;  // (the finalize works on 128-cout rows)
+  // (the finalize works on 128-cout rows)
+  p.ksplit = BN == 128 ? choose_ksplit(p, tiles, k_tiles(p, SplitBf16Opnd::KT), cx, 2) : 1;
   p.ws = cx.ws;
   cx.last_ksplit = p.ksplit;
-  hipLaunchKernelGGL((conv_x3_kernel<BM, BN, WM, WN>), dim3(tiles * p.ksplit), dim3(64 * WM * WN), lds, s, p);
-  if (p.ksplit > 1) {
-    SNRSE_LAUNCH_CHECK();
-    const int HW = p.H * p.W, ppb = 64;
-    hipLaunchKernelGGL((conv_splitk_finalize<float>), dim3(p.B * ((HW + ppb - 1) / ppb), p.Cout / 128), dim3(256), 0, s,
-                       p, ppb);
-  }
-  return (int)hipGetLastError();
+  const int rc = launch_dyn_lds<conv_x3_kernel<BM, BN, WM, WN>>(dim3(tiles * p.ksplit), dim3(64 * WM * WN), lds, s, p);
+  if (rc || p.ksplit == 1) return rc;
+  return launch_splitk_finalize<float>(p, s);
 }
 
 template <int GNM, int SPR, int TWV, int EF = EF_RT>
 int launch_x3h_ef(ConvParams p, hipStream_t s, int tiles) {
-  static const hipError_t attr = hipFuncSetAttribute((const void*)conv_x3h_kernel<GNM, SPR, TWV, EF>,
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                     (int)X3G<TWV, SPR>::LDS);
-  SNRSE_RET(attr);
   p.ntn = p.Cout / 128;
   p.ksplit = 1;
-  constexpr size_t lds = X3G<TWV, SPR>::LDS;
-  hipLaunchKernelGGL((conv_x3h_kernel<GNM, SPR, TWV, EF>), dim3(tiles), dim3(512), lds, s, p);
-  return (int)hipGetLastError();
+  return launch_dyn_lds<conv_x3h_kernel<GNM, SPR, TWV, EF>>(dim3(tiles), dim3(512), X3G<TWV, SPR>::LDS, s, p);
 }
 
 template <int GNM, int SPR, int TWV>
@@ -2152,23 +1993,14 @@ int launch_x3h(const ConvParams& p, hipStream_t s, int tiles, int spread, int tw
 template <int BM, int BN, typename T, typename TO>
 int launch_glds(ConvParams p, hipStream_t s, snrse_ctx& cx) {
   constexpr size_t lds = (size_t)3 * (BM + BN) * 128;
-  static const hipError_t attr = hipFuncSetAttribute((const void*)conv_glds_kernel<BM, BN, T, TO>,
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  SNRSE_RET(attr);
   p.ntn = p.Cout / BN;
   const int ntm = (p.M + BM - 1) / BM;
-  const int nk = p.ksize * p.ksize * ((p.C0 + p.C1) / 64) + (p.sc_src ? (p.Csc + p.Csc1) / 64 : 0);
-  p.ksplit = choose_ksplit(p, ntm * p.ntn, nk, cx);
+  p.ksplit = choose_ksplit(p, ntm * p.ntn, k_tiles(p, 64), cx);
   p.ws = cx.ws;
   cx.last_ksplit = p.ksplit;
-  hipLaunchKernelGGL((conv_glds_kernel<BM, BN, T, TO>), dim3(ntm * p.ntn * p.ksplit), dim3(512), lds, s, p);
-  if (p.ksplit > 1) {
-    SNRSE_LAUNCH_CHECK();
-    const int HW = p.H * p.W, ppb = 64;
-    hipLaunchKernelGGL((conv_splitk_finalize<TO>), dim3(p.B * ((HW + ppb - 1) / ppb), p.Cout / 128), dim3(256), 0, s,
-                       p, ppb);
-  }
-  return (int)hipGetLastError();
+  const int rc = launch_dyn_lds<conv_glds_kernel<BM, BN, T, TO>>(dim3(ntm * p.ntn * p.ksplit), dim3(512), lds, s, p);
+  if (rc || p.ksplit == 1) return rc;
+  return launch_splitk_finalize<TO>(p, s);
 }
 
 // 0 auto, 1 force v1 (register-staged), 2 force v2 (no halo), 5 halo v5; the experimental
@@ -2224,6 +2056,72 @@ int dispatch_conv(const ConvParams& p, hipStream_t s, snrse_ctx& cx) {
   return launch_conv<T, TO, 128, 16, 4, 1>(p, 16, s, cx);
 }
 
+// tiles of the fp32x3 halo GEMM: 8 x 32 px (tw 32: H % 8 == 0, W % 32 == 0) or 4 x 64 px with the last column cut by
+// the image edge, x 128 couts
+inline long long x3h_tile_count(const ConvParams& p, int tw) {
+  return (long long)p.B * (p.H / (256 / tw)) * ((p.W + tw - 1) / tw) * (p.Cout / 128);
+}
+
+// The fp32x3 dispatch (dtype SNRSE_F32X3), beside dispatch_conv.  x3h_all: the call takes the halo form.
+int dispatch_x3(const ConvParams& q, hipStream_t stream, snrse_ctx& cx, bool x3h_all) {
+  if (x3h_all) {
+    cx.last_kernel = 4;
+    cx.last_ksplit = 1;
+    // non-temporal output stores as the bf16 halo GEMMs decide them (option x3_nt: the f32 outputs of the
+    // level-0 / level-1 convs are 0.5-2 GB, far beyond the Infinity Cache)
+    ConvParams r = q;
+    r.epi_nt = cx.x3_nt && stream_output(cx, (long long)q.M * q.out_ld * 4ll) != 0;
+    cx.last_epi_nt = r.epi_nt;
+    // 8 x 32 tiles where they fit (option x3_tw: 0 auto, 64 forces 4 x 64)
+    const int tw = (cx.x3_tw != 64 && q.H % 8 == 0 && q.W % 32 == 0) ? 32 : 64;
+    cx.last_tw = tw;
+    return launch_x3h(r, stream, (int)x3h_tile_count(q, tw), cx.x3_spread, tw, cx.h5_specialise != 0);
+  }
+  if (q.Cout <= 16 && cx.conv_variant != 1 && head_ok(q, true)) {  // the pyramid heads, GroupNorm fused
+    cx.last_kernel = 11;
+    cx.last_ksplit = 1;
+    return launch_head_x3(q, stream);
+  }
+  if (q.Cout <= 16 && cx.conv_variant != 1 && cx.head_small && head_small_ok(q)) {  // small-image heads
+    cx.last_kernel = 14;
+    cx.last_ksplit = 1;
+    return launch_head_small(q, stream, true);
+  }
+  if (q.gn_scale) return SNRSE_EINVAL;  // the fused GroupNorm exists on the halo forms only
+  cx.last_kernel = 3;
+  if (q.Cout <= 16) return launch_x3<128, 16, 4, 1>(q, stream, cx);  // the pyramid heads (16 padded rows)
+  if (cx.x3_tile == 2) return launch_x3<256, 128, 4, 2>(q, stream, cx);
+  if (cx.x3_tile == 3 && q.Cout % 256 == 0) return launch_x3<128, 256, 2, 4>(q, stream, cx);
+  return launch_x3<128, 128, 2, 2>(q, stream, cx);
+}
+
+// images b0 .. b0 + nb - 1 of the call p as a call of their own (esz / osz: bytes per input / output element)
+ConvParams image_range(const ConvParams& p, int b0, int nb, long long esz, long long osz) {
+  ConvParams q = p;
+  const long long HW = (long long)p.H * p.W, px0 = (long long)b0 * HW;
+  auto off = [&](const void* ptr, long long elems, long long bytes_per) -> const void* {
+    return ptr ? (const void*)((const char*)ptr + elems * bytes_per) : nullptr;
+  };
+  const int Cin = p.C0 + p.C1;
+  q.src0 = off(p.src0, px0 * p.C0, esz);
+  q.src1 = off(p.src1, px0 * p.C1, esz);
+  q.sc_src = off(p.sc_src, px0 * p.Csc, esz);
+  q.sc_src1 = off(p.sc_src1, px0 * p.Csc1, esz);
+  q.res = off(p.res, px0 * p.res_ld, osz);
+  q.comb_src = (const float*)off(p.comb_src, px0 * 4, 4);
+  q.out = (void*)off(p.out, px0 * p.out_ld, osz);
+  q.temb = (const float*)off(p.temb, (long long)b0 * p.temb_stride, 4);
+  q.stats = p.stats ? p.stats + (size_t)b0 * SNRSE_STAT_SLOTS * p.Cout * 2 : nullptr;
+  q.gn_scale = (const float*)off(p.gn_scale, (long long)b0 * Cin, 4);
+  q.gn_shift = (const float*)off(p.gn_shift, (long long)b0 * Cin, 4);
+  q.B = nb;
+  q.M = nb * p.H * p.W;
+  const long long qpix = (long long)nb * HW;
+  q.bytes0 = qpix * p.C0 * esz; q.bytes1 = qpix * p.C1 * esz;
+  q.sc_bytes0 = qpix * p.Csc * esz; q.sc_bytes1 = qpix * p.Csc1 * esz;
+  return q;
+}
+
 }  // namespace
 
 extern "C" int snrse_conv2d(snrse_ctx* ctx, const void* src0, int C0, const void* src1, int C1, int B, int H, int W,
@@ -2234,8 +2132,6 @@ extern "C" int snrse_conv2d(snrse_ctx* ctx, const void* src0, int C0, const void
                             const float* comb_b, void* out, int Cout, int out_ld, double* stats,
                             const float* gn_scale, const float* gn_shift, int gn_act, int dtype,
                             int out_f32, hipStream_t stream) {
-  using TrB = ConvTraits<bf16_t>;  // (f16: the same 64-element K-tiles)
-  using TrF = ConvTraits<float>;
   snrse_ctx& cx = *snrse_ctx_resolve(ctx);
   // SNRSE_F32X3: fp32 activations / output, weights pre-split into bf16 hi / lo rows (conv_x3_kernel)
   const bool x3 = dtype == SNRSE_F32X3;
@@ -2244,7 +2140,8 @@ extern "C" int snrse_conv2d(snrse_ctx* ctx, const void* src0, int C0, const void
     dtype = SNRSE_F32;
     out_f32 = 0;  // (the output is fp32 anyway)
   }
-  const int KT = snrse_is16(dtype) ? TrB::KT : TrF::KT;
+  const long long esz = snrse_is16(dtype) ? 2 : 4, osz = (snrse_is16(dtype) && !out_f32) ? 2 : 4;
+  const int KT = esz == 2 ? ConvTraits<bf16_t>::KT : ConvTraits<float>::KT;  // (f16: the same 64-element K-tiles)
   if (!src0 || !wgt || !out || (ksize != 1 && ksize != 3)) return SNRSE_EINVAL;
   if (C0 % KT || C1 % KT || (sc_src && (Csc % KT || Csc1 % KT))) return SNRSE_EINVAL;
   if (sc_src && Csc1 > 0 && !sc_src1) return SNRSE_EINVAL;
@@ -2268,8 +2165,6 @@ extern "C" int snrse_conv2d(snrse_ctx* ctx, const void* src0, int C0, const void
   p.ws = nullptr; p.ksplit = 1;
   p.gn_scale = gn_scale; p.gn_shift = gn_shift; p.gn_act = gn_act;
   if ((gn_scale == nullptr) != (gn_shift == nullptr)) return SNRSE_EINVAL;
-  if (p.M <= 0) return 0;
-  const long long esz = snrse_is16(dtype) ? 2 : 4;
   const long long pix = (long long)B * H * W;
   p.bytes0 = pix * C0 * esz; p.bytes1 = pix * C1 * esz;
   p.sc_bytes0 = pix * p.Csc * esz; p.sc_bytes1 = pix * p.Csc1 * esz;
@@ -2277,49 +2172,16 @@ extern "C" int snrse_conv2d(snrse_ctx* ctx, const void* src0, int C0, const void
   p.wbytes = (long long)npad * ksize * ksize * (C0 + C1) * esz;
   p.sc_wbytes = (long long)npad * (p.Csc + p.Csc1) * esz;
   p.ntn = 1;
+  if (p.M <= 0) return 0;
   if (stats && !cx.stats_zeroed) SNRSE_RET(hipMemsetAsync(stats, 0, sizeof(double) * 2 * SNRSE_STAT_SLOTS * (size_t)B * Cout, stream));
   if (!snrse_is16(dtype) && dtype != SNRSE_F32) return SNRSE_EINVAL;
   // the split-bf16 halo-kernel decision is taken once for the whole batch (as ops.x3h_ok takes it, which
   // decides whether the caller passes a GroupNorm prologue), so every image-range chunk of a > 2 GiB call
   // runs the same kernel, however few tiles its last chunk has
   const bool x3h_all = x3 && ksize == 3 && H % x3h::TH == 0 && Cout % 128 == 0 &&
-                       ((cx.x3_tile == 0 && (long long)B * (H / x3h::TH) * ((W + x3h::TW - 1) / x3h::TW) * (Cout / 128) >= 256) ||
-                        cx.x3_tile == 4);
+                       ((cx.x3_tile == 0 && x3h_tile_count(p, x3h::TW) >= 256) || cx.x3_tile == 4);
   auto run = [&](const ConvParams& q) {
-    if (x3) {
-      const int x3h_tiles = q.B * (q.H / x3h::TH) * ((q.W + x3h::TW - 1) / x3h::TW) * (q.Cout / 128);
-      if (x3h_all) {
-        cx.last_kernel = 4;
-        cx.last_ksplit = 1;
-        // non-temporal output stores as the bf16 halo GEMMs decide them (option x3_nt: the f32 outputs of the
-        // level-0 / level-1 convs are 0.5-2 GB, far beyond the Infinity Cache)
-        ConvParams r = q;
-        r.epi_nt = cx.x3_nt && (cx.epi_nt == 2 ? ((long long)q.M * q.out_ld * 4ll > ((long long)cx.epi_nt_mb << 20))
-                                               : cx.epi_nt != 0);
-        cx.last_epi_nt = r.epi_nt;
-        // 8 x 32 tiles where they fit (option x3_tw: 0 auto, 64 forces 4 x 64)
-        const bool tw32 = cx.x3_tw != 64 && q.H % 8 == 0 && q.W % 32 == 0;
-        cx.last_tw = tw32 ? 32 : 64;
-        return launch_x3h(r, stream, tw32 ? q.B * (q.H / 8) * (q.W / 32) * (q.Cout / 128) : x3h_tiles, cx.x3_spread,
-                          tw32 ? 32 : 64, cx.h5_specialise != 0);
-      }
-      if (q.Cout <= 16 && cx.conv_variant != 1 && head_ok(q, true)) {  // the pyramid heads, GroupNorm fused
-        cx.last_kernel = 11;
-        cx.last_ksplit = 1;
-        return launch_head_x3(q, stream);
-      }
-      if (q.Cout <= 16 && cx.conv_variant != 1 && cx.head_small && head_small_ok(q)) {  // small-image heads
-        cx.last_kernel = 14;
-        cx.last_ksplit = 1;
-        return launch_head_small(q, stream, true);
-      }
-      if (q.gn_scale) return SNRSE_EINVAL;  // the fused GroupNorm exists on the halo forms only
-      cx.last_kernel = 3;
-      if (q.Cout <= 16) return launch_x3<128, 16, 4, 1>(q, stream, cx);  // the pyramid heads (16 padded rows)
-      if (cx.x3_tile == 2) return launch_x3<256, 128, 4, 2>(q, stream, cx);
-      if (cx.x3_tile == 3 && q.Cout % 256 == 0) return launch_x3<128, 256, 2, 4>(q, stream, cx);
-      return launch_x3<128, 128, 2, 2>(q, stream, cx);
-    }
+    if (x3) return dispatch_x3(q, stream, cx, x3h_all);
     if (dtype == SNRSE_F16)
       return out_f32 ? dispatch_conv<f16_t, float>(q, stream, cx) : dispatch_conv<f16_t, f16_t>(q, stream, cx);
     if (dtype == SNRSE_BF16)
@@ -2342,32 +2204,8 @@ extern "C" int snrse_conv2d(snrse_ctx* ctx, const void* src0, int C0, const void
   if (per_img * B < kLim || per_img >= kLim) return run(p);
   const int chunk = (int)((kLim - 1) / per_img);
   cx.last_chunks = (B + chunk - 1) / chunk;
-  const long long HWl = (long long)H * W;
   for (int b0 = 0; b0 < B; b0 += chunk) {
-    const int nb = std::min(chunk, B - b0);
-    ConvParams q = p;
-    const long long px0 = (long long)b0 * HWl;
-    auto off = [&](const void* ptr, long long elems, long long bytes_per) -> const void* {
-      return ptr ? (const void*)((const char*)ptr + elems * bytes_per) : nullptr;
-    };
-    const long long osz = (snrse_is16(dtype) && !out_f32) ? 2 : 4;
-    q.src0 = off(p.src0, px0 * C0, esz);
-    q.src1 = off(p.src1, px0 * C1, esz);
-    q.sc_src = off(p.sc_src, px0 * p.Csc, esz);
-    q.sc_src1 = off(p.sc_src1, px0 * p.Csc1, esz);
-    q.res = off(p.res, px0 * res_ld, osz);
-    q.comb_src = (const float*)off(p.comb_src, px0 * 4, 4);
-    q.out = (void*)off(p.out, px0 * out_ld, osz);
-    q.temb = (const float*)off(p.temb, (long long)b0 * temb_stride, 4);
-    q.stats = p.stats ? p.stats + (size_t)b0 * SNRSE_STAT_SLOTS * Cout * 2 : nullptr;
-    q.gn_scale = (const float*)off(p.gn_scale, (long long)b0 * (C0 + C1), 4);
-    q.gn_shift = (const float*)off(p.gn_shift, (long long)b0 * (C0 + C1), 4);
-    q.B = nb;
-    q.M = nb * H * W;
-    const long long qpix = (long long)nb * HWl;
-    q.bytes0 = qpix * C0 * esz; q.bytes1 = qpix * C1 * esz;
-    q.sc_bytes0 = qpix * p.Csc * esz; q.sc_bytes1 = qpix * p.Csc1 * esz;
-    const int rc = run(q);
+    const int rc = run(image_range(p, b0, std::min(chunk, B - b0), esz, osz));
     if (rc) return rc;
   }
   return 0;

@@ -41,13 +41,13 @@ struct ConvParams {
   void* out; int Cout; int out_ld;
   double* stats;  // optional [B][SLOTS][Cout][2] per-channel (sum, sumsq) of the output (zeroed by launcher)
   int M;
-  int ntn;        // N tiles (v2 grid)
-  long long bytes0, bytes1, sc_bytes0, sc_bytes1, wbytes, sc_wbytes;  // buffer extents (v2)
+  int ntn;        // N tiles of the grid
+  long long bytes0, bytes1, sc_bytes0, sc_bytes1, wbytes, sc_wbytes;  // buffer extents (buffer-resource loads)
   const float* gn_scale;  // optional [B][Cin] GroupNorm scale/shift applied to the main input (halo path)
   const float* gn_shift;
   int gn_act;             // SiLU after the GroupNorm affine
   float* ws;              // split-K partial sums [ksplit][M][Cout] f32 (caller-registered workspace)
-  int ksplit;             // K splits of the v2 GEMM (1: the epilogue runs in the GEMM itself)
+  int ksplit;             // K splits of the GEMM (1: the epilogue runs in the GEMM itself)
   unsigned long long* stamps;  // timing-diagnostic build only (-DSNRSE_STAMPS): [blocks][8][32]
   int epi_nt;      // image-tile epilogue: non-temporal output stores
 };
@@ -107,6 +107,53 @@ SNRSE_DEV __amdgpu_buffer_rsrc_t make_rsrc(const void* base, long long bytes) {
   const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
   const int n = __builtin_amdgcn_readfirstlane((int)bytes);
   return __builtin_amdgcn_make_buffer_rsrc((void*)(((uint64_t)hi << 32) | lo), 0, n, 0x00020000);
+}
+
+// Split-K: a wave's FM x FN fragments (rows m_base.., columns n_base..) as raw fp32 partial sums into plane ks of the
+// workspace; conv_splitk_finalize sums the planes and applies the epilogue
+template <int FM, int FN>
+SNRSE_DEV void store_splitk_partials(const ConvParams& p, const f32x4 (&acc)[FM][FN], int ks, int m_base, int n_base,
+                                     int lane) {
+  const int lrow = lane & 15, lg = lane >> 4;
+  float* const wsp = p.ws + (size_t)ks * p.M * p.Cout;
+#pragma unroll
+  for (int i = 0; i < FM; ++i)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int m = m_base + i * 16 + lg * 4 + e;
+      if (m < p.M) {
+#pragma unroll
+        for (int j = 0; j < FN; ++j) wsp[(size_t)m * p.Cout + n_base + j * 16 + lrow] = acc[i][j][e];
+      }
+    }
+}
+
+// Epilogue pieces on one 16-B chunk of outputs (8 16-bit or 4 f32 values v[] of type TO):
+// v += the residual chunk rv
+template <typename TO>
+SNRSE_DEV void epi_residual(const u32x4 rv, float* v) {
+  if constexpr (sizeof(TO) == 2) {  // (unpack8's halves, added as they are converted: the order the schedules were tuned with)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      v[2 * k] += H16<TO>::lo(rv[k]);
+      v[2 * k + 1] += H16<TO>::hi(rv[k]);
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] += __uint_as_float(rv[k]);
+  }
+}
+// v -> the 16-B output chunk
+template <typename TO>
+SNRSE_DEV u32x4 epi_pack(const float* v) {
+  if constexpr (sizeof(TO) == 2) {
+    return pack8<TO>(v);
+  } else {
+    u32x4 o;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) o[k] = __float_as_uint(v[k]);
+    return o;
+  }
 }
 
 // Pyramid heads (conv_head.hip): 3x3, Cout <= 16, f32 output, optional fused GroupNorm+SiLU.

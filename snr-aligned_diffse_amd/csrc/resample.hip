@@ -310,10 +310,8 @@ __global__ __launch_bounds__(256) void gn_resample_rows_kernel(const E* __restri
                                                                int sp_img, int nt) {
   using V = RVec<E, CPT>;
   constexpr int C = NV * CPT, SPB = 256 / NV;  // strips per block
-  // XCD-aware bijective remap: consecutive logical blocks (neighbouring output rows, which share input
-  // rows) run on one XCD and its L2
-  const int q8 = nblk >> 3, r8 = nblk & 7, xcd = blockIdx.x & 7, pos = blockIdx.x >> 3;
-  const int lb = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + pos;
+  // consecutive logical blocks (neighbouring output rows, which share input rows) run on one XCD and its L2
+  const int lb = xcd_block_id(blockIdx.x, nblk);
   const int v = threadIdx.x % NV;
   const int gs = lb * SPB + threadIdx.x / NV;
   const int b = __builtin_amdgcn_readfirstlane(gs / sp_img);
