@@ -1406,8 +1406,8 @@ __global__ __launch_bounds__(256) void conv_splitk_finalize(ConvParams p, int pp
 
 // SCD: the fused 1x1 shortcut's chunks run as LDS-DMA phases interleaved with the main chunks (round 5): a shortcut
 // phase stages its 128 x 32 weights AND its unpadded 256-px x 32-channel input tile (8 + 16 KB = one ring slot) by
-// LDS-DMA, issued at the start of the phase before it like any weight phase, so the tile's HBM latency is covered by
-// that phase's MFMAs (3 taps where a main phase precedes it).  Main chunk c carries k = sb(c + 1) - sb(c) shortcut
+// LDS-DMA, issued in the first tap of the phase before it like any weight phase, so the tile's HBM latency is covered
+// by the rest of that phase (2 more taps where a main phase precedes it).  Main chunk c carries k = sb(c + 1) - sb(c) shortcut
 // phases (sb(c) = c Csc / Cin chunks): k = 0: M0 M1 M2 | 1: M0 M1 M2 S | 2: M0 M1 S M2 S | >= 3: M0 S M1 S M2 S S..;
 // the next chunk's halo is stored in the shortcut phase after M2 (which reads no halo), so that chunk boundary needs
 // no extra barrier.  (Round 4 ran the shortcut chunks after the main ones as one-tap chunks staged through registers
@@ -1459,6 +1459,43 @@ __global__ __launch_bounds__(256, 2) void conv_halo5_kernel(ConvParams p) {
   const int K1 = 9 * Cin;
   const int hcol = tid & 3;  // this thread's 16-B chunk (8 channels) of its halo rows
 
+  // LDS-DMA of a phase into a ring slot: main (c, tap group g) = 3 weight taps; shortcut u = its weight tap (8 KB)
+  // + its input tile (16 KB, tile row r = pixel (r / TW, r % TW), 64-B rows, chunk swizzle on the source).
+  // A wave issues 6 pieces of 1 KB (16 rows x 64 B) per phase.  What differs between the lanes of a piece's source
+  // address is constant over the tile and kept in one VGPR (wlane; sclane, xpix for the shortcut); what changes per
+  // piece and per phase is wave-uniform and goes in the buffer instruction's scalar offset, advanced by scalar adds.
+  // The descriptors are built once.  Main piece k: tap k >> 1, cout rows (wid + 4 (k & 1)) 16 + rl.
+  // After the last phase the same 6 pieces are issued out of range through the VGPR offset (bit 31: no memory access,
+  // zeros land in the free ring slot), so every phase issues a fixed count (vm_after_dma).
+  const int rl = lane >> 2, swz8 = ((lane & 3) ^ ((rl >> 1) & 3)) * 8;
+  const __amdgpu_buffer_rsrc_t wrsrc = make_rsrc(p.wgt, p.wbytes);
+  const unsigned wlane = (unsigned)(((n0 + wid * 16 + rl) * K1 + swz8) * 2);
+  const unsigned wrow64 = (unsigned)(64 * K1 * 2), wtap = (unsigned)(Cin * 2);  // + 64 cout rows, + 1 tap
+  using lds_ptr = __attribute__((address_space(3))) void*;
+  // piece k of a main phase with the phase offset soff (woff) and the per-lane offset vl (wlane, or out of range)
+  auto dma_w = [&](auto k_, unsigned vl, unsigned soff, char* dst) {
+    constexpr int k = decltype(k_)::value;
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(wrsrc, (lds_ptr)(dst + (k >> 1) * TAPB + (wid + 4 * (k & 1)) * 1024), 16,
+                                             vl, soff + (k & 1) * wrow64 + (k >> 1) * wtap, 0, 0);
+  };
+  // the phase offset of main (c, g): tap 3 g, channel 32 c
+  auto woff = [&](int c, int g) { return (unsigned)((3 * g * Cin + c * KT) * 2); };
+
+  u32x4 hv[HJ];
+  f32x4 gnv;  // lanes 0..15 of wave 0: 4 of the next chunk's 64 GroupNorm scale / shift values
+  auto gn_load = [&](int c) {  // wave 0's load of chunk c's GroupNorm affine
+    if constexpr (GNM > 0) {
+      if (tid < 16)
+        gnv = *(const f32x4*)((tid < 8 ? p.gn_scale : p.gn_shift) + (size_t)bb * Cin + c * KT + (tid & 7) * 4);
+    }
+  };
+
+  // the tile's first memory requests, ahead of the halo's divide-by-HC address arithmetic: phase 0's weights and
+  // chunk 0's GroupNorm affine
+  static_for<6>([&](auto k) { dma_w(k, wlane, 0u, ring); });
+  gn_load(0);
+  __builtin_amdgcn_sched_barrier(0);
+
   int hpix[HJ];
   bool hok[HJ];
 #pragma unroll
@@ -1469,9 +1506,6 @@ __global__ __launch_bounds__(256, 2) void conv_halo5_kernel(ConvParams p) {
     hok[j] = hr < HROWS && ih >= 0 && ih < p.H && iw >= 0 && iw < p.W;
     hpix[j] = (bb * p.H + ih) * p.W + iw;
   }
-
-  u32x4 hv[HJ];
-  f32x4 gnv;  // lanes 0..15 of wave 0: 4 of the next chunk's 64 GroupNorm scale / shift values
 
 #define SNRSE_HALO5_LOADS(BASE_, BYTES_, CS_, CC_)                                                     \
   do {                                                                                              \
@@ -1488,9 +1522,6 @@ __global__ __launch_bounds__(256, 2) void conv_halo5_kernel(ConvParams p) {
     // compiler's waitcnt model assume the other branch's loads pending: a vmcnt(0) on every src1 chunk)
     const bool s1 = ch >= p.C0;
     SNRSE_HALO5_LOADS(s1 ? p.src1 : p.src0, s1 ? p.bytes1 : p.bytes0, s1 ? p.C1 : p.C0, s1 ? ch - p.C0 : ch);
-    if constexpr (GNM > 0) {
-      if (tid < 16) gnv = *(const f32x4*)((tid < 8 ? p.gn_scale : p.gn_shift) + (size_t)bb * Cin + ch + (tid & 7) * 4);
-    }
   };
 #undef SNRSE_HALO5_LOADS
   auto gn_publish = [&]() {  // before the barrier that precedes halo_store
@@ -1524,52 +1555,6 @@ __global__ __launch_bounds__(256, 2) void conv_halo5_kernel(ConvParams p) {
       *(u32x4*)(halo + swz64(hr, hcol)) = v;
     }
   };
-  // LDS-DMA of a phase into ring slot dst: main (c, tap group g) = 3 weight taps; shortcut u = its weight tap
-  // (8 KB) + its input tile (16 KB, tile row r = pixel (r / TW, r % TW), 64-B rows, chunk swizzle on the source)
-  // oob: the phase after the last one -- the same 6 pieces per wave, out of range (no memory access; zeros land in the
-  // free ring slot), so every phase issues a fixed count (vm_after_dma)
-  auto dma = [&](int c, int g, int u, char* dst, bool oob = false) {
-    const int rl = lane >> 2, sl = lane & 3;
-    const unsigned oobm = oob ? 0x80000000u : 0u;
-    if (g < 3) {
-      const __amdgpu_buffer_rsrc_t r = make_rsrc(p.wgt, p.wbytes);
-      const int kb = c * KT;
-      // (a compile-time count per wave: 6 pieces, so the compiler's waitcnt model can count them -- vm_after_dma)
-#pragma unroll
-      for (int k = 0; k < 6; ++k) {
-        const int ii = wid + 4 * k;
-        const int jt = ii >> 3, pc = ii & 7;
-        const int row = pc * 16 + rl;
-        const unsigned voff = oobm | (unsigned)(((n0 + row) * K1 + (3 * g + jt) * Cin + kb + (sl ^ ((row >> 1) & 3)) * 8) * 2);
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(
-            r, (__attribute__((address_space(3))) void*)(dst + jt * TAPB + pc * 1024), 16, voff, 0, 0, 0);
-      }
-    } else {
-      const __amdgpu_buffer_rsrc_t r = make_rsrc(p.sc_wgt, p.sc_wbytes);
-      const int kb = u * KT;
-#pragma unroll
-      for (int k = 0; k < 2; ++k) {
-        const int pc = wid + 4 * k;
-        const int row = pc * 16 + rl;
-        const unsigned voff = oobm | (unsigned)(((n0 + row) * Csc_all + kb + (sl ^ ((row >> 1) & 3)) * 8) * 2);
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(
-            r, (__attribute__((address_space(3))) void*)(dst + pc * 1024), 16, voff, 0, 0, 0);
-      }
-      const bool one = kb >= p.Csc;
-      const __amdgpu_buffer_rsrc_t rx = one ? make_rsrc(p.sc_src1, p.sc_bytes1) : make_rsrc(p.sc_src, p.sc_bytes0);
-      const int cs = one ? p.Csc1 : p.Csc, cb = one ? kb - p.Csc : kb;
-      const int pix0 = (bb * p.H + h0) * p.W + w0;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int pc = wid + 4 * k;
-        const int row = pc * 16 + rl;
-        const int pix = pix0 + (row / TW) * p.W + row % TW;
-        const unsigned voff = oobm | (unsigned)((pix * cs + cb + (sl ^ ((row >> 1) & 3)) * 8) * 2);
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(
-            rx, (__attribute__((address_space(3))) void*)(dst + TAPB + pc * 1024), 16, voff, 0, 0, 0);
-      }
-    }
-  };
   f32x4 acc[2][4][4];
 #pragma unroll
   for (int h = 0; h < 2; ++h)
@@ -1588,7 +1573,15 @@ __global__ __launch_bounds__(256, 2) void conv_halo5_kernel(ConvParams p) {
 
   if constexpr (SCD) {
     // ---- main chunks with their shortcut phases interleaved (see the kernel comment) ----
-    auto nsc = [&](int c) { return (c + 1) * cbs / cbm - c * cbs / cbm; };
+    // shortcut chunks of main chunk c: sb(c + 1) - sb(c), by a remainder counter (cbs = kq cbm + kr)
+    const int kq = cbs / cbm, kr = cbs - kq * cbm;
+    int krem = 0;
+    auto nsc_next = [&]() {
+      krem += kr;
+      const bool wrap = krem >= cbm;
+      if (wrap) krem -= cbm;
+      return kq + (wrap ? 1 : 0);
+    };
     // kind of position s of a chunk with k shortcut phases: 0..2 = main tap group t0 = 3 kind, 3 = shortcut (su: its
     // ordinal in the chunk)
     auto kind_of = [](int s, int k, int& su) -> int {
@@ -1609,8 +1602,15 @@ __global__ __launch_bounds__(256, 2) void conv_halo5_kernel(ConvParams p) {
       return 3;
     };
     auto m2_pos = [](int k) { return k >= 3 ? 4 : k == 2 ? 3 : 2; };  // position of M2
+    // the shortcut phases' sources, like the weights': descriptors built once, one per-lane VGPR each (sclane: the
+    // 1x1 weights' cout row; xpix: the pixel of this lane's tile row of piece 0 -- piece k is 64 k tile rows on)
+    const __amdgpu_buffer_rsrc_t scrsrc = make_rsrc(p.sc_wgt, p.sc_wbytes);
+    const __amdgpu_buffer_rsrc_t xrsrc0 = make_rsrc(p.sc_src, p.sc_bytes0), xrsrc1 = make_rsrc(p.sc_src1, p.sc_bytes1);
+    const unsigned sclane = (unsigned)(((n0 + wid * 16 + rl) * Csc_all + swz8) * 2);
+    const unsigned scrow64 = (unsigned)(64 * Csc_all * 2);
+    const int trow = wid * 16 + rl;
+    const int xpix = (bb * p.H + h0 + trow / TW) * p.W + w0 + trow % TW;
     halo_load(0);
-    dma(0, 0, 0, ring);
     if constexpr (GNM > 0) {
       gn_publish();
       __syncthreads();
@@ -1619,13 +1619,12 @@ __global__ __launch_bounds__(256, 2) void conv_halo5_kernel(ConvParams p) {
     // halo loads issued after a phase's DMA: each thread's HJ vectors (+ wave 0's GroupNorm affine load)
     const bool w0g = GNM > 0 && wid == 0;
     bool halo_inflight = false;
-    int c = 0, pos = 0, k = nsc(0), ub = 0;  // current phase: chunk c, position pos; ub = sb(c)
+    int c = 0, pos = 0, k = nsc_next(), ub = 0;  // current phase: chunk c, position pos; ub = sb(c)
+    int su, kind = kind_of(0, k, su);
     for (int q = 0; q < nq; ++q) {
-      int su;
-      const int kind = kind_of(pos, k, su);
-      // the next phase
+      // the next phase (its kind is carried into the next iteration)
       int c2 = c, pos2 = pos + 1, k2 = k, ub2 = ub;
-      if (pos2 == 3 + k) { c2 = c + 1; pos2 = 0; ub2 = ub + k; k2 = c2 < cbm ? nsc(c2) : 0; }
+      if (pos2 == 3 + k) { c2 = c + 1; pos2 = 0; ub2 = ub + k; k2 = c2 < cbm ? nsc_next() : 0; }
       int su2;
       const int kind2 = kind_of(pos2, k2, su2);
       if (halo_inflight) {
@@ -1635,23 +1634,56 @@ __global__ __launch_bounds__(256, 2) void conv_halo5_kernel(ConvParams p) {
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
       }
       __builtin_amdgcn_s_barrier();
-      dma(c2 < cbm ? c2 : 0, kind2, ub2 + su2, ring + ((q + 1) & 1) * SLOT, q + 1 >= nq);
-      halo_inflight = false;
-      if (kind == 0 && c + 1 < cbm) {
-        vm_after_dma();
-        halo_load(c + 1);
-        halo_inflight = true;
+      char* const nx = ring + ((q + 1) & 1) * SLOT;
+      // The next phase's 6 pieces go into the slot read in the previous phase (free now that every wave has passed
+      // the barrier), as 3 pairs (k, k + 1) issued in MFMA gaps below.  Pair 0 is (Rc, Vc, Sc, Dc), the pairs after
+      // it start at (Rn, Vn, Sn, Dn) and advance by (DPn, DDn); the odd piece of a pair is + O in the source and
+      // + 4 KB in the slot.  Main: pair = tap, odd = + 64 cout rows.  Shortcut: pair 0 = the 1x1 weights, pairs 1, 2
+      // = the input tile (odd = + 64 tile rows).
+      __amdgpu_buffer_rsrc_t Rc, Rn;
+      unsigned Vc, Vn, Sc, Sn, Oc, On, DPn;
+      int DDn;
+      char* Dc = nx + wid * 1024;
+      char* Dn = Dc + TAPB;
+      if (kind2 < 3) {
+        const bool fin = q + 1 >= nq;  // (the phase after the last is a main one: chunk cbm, position 0)
+        Rc = Rn = wrsrc;
+        Vc = Vn = fin ? wlane | 0x80000000u : wlane;
+        Sc = fin ? 0u : woff(c2, kind2);
+        Sn = Sc + wtap; DPn = wtap; DDn = TAPB;
+        Oc = On = wrow64;
+      } else {
+        const int kb = (ub2 + su2) * KT;
+        const bool one = kb >= p.Csc;
+        const int cs = one ? p.Csc1 : p.Csc, cb = one ? kb - p.Csc : kb;
+        const unsigned xstep = (unsigned)((64 / TW) * p.W * cs * 2);
+        Rc = scrsrc; Vc = sclane; Sc = (unsigned)(kb * 2); Oc = scrow64;
+        Rn = one ? xrsrc1 : xrsrc0;
+        Vn = (unsigned)((xpix * cs + swz8) * 2);
+        Sn = (unsigned)(cb * 2); On = xstep; DPn = 2 * xstep; DDn = 8192;
       }
-      // one MFMA code path for both kinds (two would double-allocate the accumulators): a main phase reads its 3 taps'
-      // A fragments from the halo (row stride HC), a shortcut phase its one tap from the slot's input tile (stride TW)
+      auto dma_pair = [&]() {
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(Rc, (lds_ptr)Dc, 16, Vc, Sc, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(Rc, (lds_ptr)(Dc + 4096), 16, Vc, Sc + Oc, 0, 0);
+        Rc = Rn; Vc = Vn; Sc = Sn; Oc = On; Dc = Dn;
+        Sn += DPn; Dn += DDn;
+      };
+      // one tap body for both kinds: a main phase reads its 3 taps' A fragments from the halo (row stride HC), a
+      // shortcut phase its one tap from the slot's input tile (stride TW).  Tap 0, which every phase has, is peeled
+      // and carries the 3 pairs after its 8th, 16th and 24th MFMA (pinned by the sched_group_barrier sequence; 0x008:
+      // MFMA, 0x020: vector-memory read), so the piece count per phase stays a compile-time 6 and every piece has
+      // the rest of the phase + the next phase top as cover; taps 1, 2 run in the rolled loop.  The two instances of
+      // the body share the accumulators: no scratch, 2 workgroups per CU.  Issuing the pairs from
+      // inside one rolled body behind wave-uniform branches was 1.4 % slower than issuing them at the phase top.
       const char* sl = ring + (q & 1) * SLOT;
       const bool mainph = kind < 3;
       const char* abuf = mainph ? halo : sl + TAPB;
       const int ntap = mainph ? 3 : 1, rs = mainph ? HC : TW;
-      for (int jt = 0; jt < ntap; ++jt) {
-        const int tp = 3 * kind + jt;
-        const int dy = tp / 3 - 1, dx = tp - (tp / 3) * 3 - 1;
-        const int arow = mainph ? (wid * RW + dy + 1) * HC + dx + 1 + lrow : wid * RW * TW + lrow;
+      // tap 3 kind + jt of a main phase: halo row offset dy + 1 = kind, column offset dx + 1 = jt
+      const int arow0 = mainph ? (wid * RW + kind) * HC + lrow : wid * RW * TW + lrow;
+      auto tap_body = [&](int jt, auto gap_) {
+        constexpr bool gap = decltype(gap_)::value;  // tap 0: the next phase's 3 pairs in its MFMA gaps
+        const int arow = arow0 + jt;
         const char* sb = sl + jt * TAPB;
         u32x4 af[4], bfr[8];
         // fragment i: pixels 16 i .. 16 i + 15 of the wave's 64 = image row (16 i) / TW, column (16 i) % TW
@@ -1659,12 +1691,32 @@ __global__ __launch_bounds__(256, 2) void conv_halo5_kernel(ConvParams p) {
         for (int i = 0; i < 4; ++i) af[i] = *(const u32x4*)(abuf + swz64(arow + (16 * i / TW) * rs + (16 * i) % TW, lg));
 #pragma unroll
         for (int j = 0; j < 8; ++j) bfr[j] = *(const u32x4*)(sb + swz64(j * 16 + lrow, lg));
+        static_for<32>([&](auto m_) {
+          constexpr int m = decltype(m_)::value, h = m >> 4, i = (m >> 2) & 3, j = m & 3;
+          acc[h][i][j] = mfma_chunk<T>(af[i], bfr[h * 4 + j], acc[h][i][j]);
+          if constexpr (gap && (m & 7) == 7 && m < 24) dma_pair();
+        });
+        if constexpr (gap) {
 #pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-          for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[h][i][j] = mfma_chunk<T>(af[i], bfr[h * 4 + j], acc[h][i][j]);
+          for (int u = 0; u < 3; ++u) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
+            __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);
+          }
+          __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
+        }
+      };
+      tap_body(0, std::true_type{});
+#pragma nounroll
+      for (int jt = 1; jt < ntap; ++jt) tap_body(jt, std::false_type{});
+      if (kind == 0 && c + 1 < cbm) {
+        // the next chunk's halo, younger than this phase's pieces: the next phase top's vmcnt(HJ [+ 1]) retires the
+        // pieces and leaves these in flight for one more phase
+        vm_after_dma();
+        halo_load(c + 1);
+        gn_load(c + 1);
+        halo_inflight = true;
+      } else {
+        halo_inflight = false;
       }
       if (c + 1 < cbm) {
         if (kind == 2) {
@@ -1680,12 +1732,11 @@ __global__ __launch_bounds__(256, 2) void conv_halo5_kernel(ConvParams p) {
           halo_store(c + 1);  // the first shortcut phase after M2: no wave reads the halo here
         }
       }
-      c = c2; pos = pos2; k = k2; ub = ub2;
+      c = c2; pos = pos2; k = k2; ub = ub2; kind = kind2; su = su2;
     }
   } else {
   // no shortcut: 3 phases of 3 taps per chunk, the next chunk's halo stored behind one more barrier
   halo_load(0);
-  dma(0, 0, 0, ring);
   if constexpr (GNM > 0) {
     gn_publish();
     __syncthreads();
@@ -1694,11 +1745,15 @@ __global__ __launch_bounds__(256, 2) void conv_halo5_kernel(ConvParams p) {
   SNRSE_STAMP(1);
   bool halo_inflight = false;
   const bool w0g = GNM > 0 && wid == 0;
+  // phase q = (chunk c, tap group g); counters, no divisions.  soff: the weight offset of phase q + 1 = (c, g + 1) or
+  // (c + 1, 0), advanced by 3 taps or back by 6 taps and on by one chunk
+  int c = 0, g = 0;
+  unsigned soff = woff(0, 1);
+  const unsigned soff_g = 3 * wtap, soff_c = (unsigned)(2 * KT) - 6 * wtap;
   for (int q = 0; q < nq; ++q) {
-    const int c = q / 3, t0 = (q - c * 3) * 3;
-    const bool first = t0 == 0, last = t0 == 6;
+    const bool first = g == 0, last = g == 2;
     // the halo prefetch issued after the previous phase's weights may stay in flight (HJ vectors + wave 0's
-    // GroupNorm affine load)
+    // GroupNorm affine load); the 6 weight pieces are older and have landed after this wait
     if (halo_inflight) {
       if (w0g) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(HJ + 1) : "memory");
       else asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(HJ) : "memory");
@@ -1707,18 +1762,18 @@ __global__ __launch_bounds__(256, 2) void conv_halo5_kernel(ConvParams p) {
     }
     __builtin_amdgcn_s_barrier();
     SNRSE_STAMP(2 + 2 * (q & 15));
-    dma(q + 1 < nq ? (q + 1) / 3 : 0, (q + 1) % 3, 0, ring + ((q + 1) & 1) * SLOT, q + 1 >= nq);
-    halo_inflight = false;
-    if (first && c + 1 < cbm) {
-      vm_after_dma();
-      halo_load(c + 1);
-      halo_inflight = !last && q + 1 < nq;
-    }
+    // The next phase's 6 pieces go into the slot that was read in the previous phase: free now that every wave has
+    // passed the barrier.  They are issued in the MFMA gaps of taps 0 and 1 (one after every 8 MFMAs), so that the
+    // first fragment reads and MFMAs of this phase do not wait behind their issue, and every piece still has tap 2
+    // (512 MFMA cycles) + the next phase top as cover.
+    const bool fin = q + 1 >= nq;
+    const unsigned vl = fin ? wlane | 0x80000000u : wlane, so = fin ? 0u : soff;
+    char* const nx = ring + ((q + 1) & 1) * SLOT;
     const char* sl = ring + (q & 1) * SLOT;
-    for (int jt = 0; jt < 3; ++jt) {
-      const int tp = t0 + jt;
-      const int dy = tp / 3 - 1, dx = tp - (tp / 3) * 3 - 1;
-      const int hbase = (wid * RW + dy + 1) * HC + dx + 1 + lrow;
+    const int hrow = (wid * RW + g) * HC + lrow;  // tap 3 g + jt: halo row offset dy + 1 = g, column offset dx + 1 = jt
+    static_for<3>([&](auto jt_) {
+      constexpr int jt = decltype(jt_)::value;
+      const int hbase = hrow + jt;
       const char* sb = sl + jt * TAPB;
       u32x4 af[4], bfr[8];
       // fragment i: pixels 16 i .. 16 i + 15 of the wave's 64 = image row (16 i) / TW, column (16 i) % TW
@@ -1726,15 +1781,37 @@ __global__ __launch_bounds__(256, 2) void conv_halo5_kernel(ConvParams p) {
       for (int i = 0; i < 4; ++i) af[i] = *(const u32x4*)(halo + swz64(hbase + (16 * i / TW) * HC + (16 * i) % TW, lg));
 #pragma unroll
       for (int j = 0; j < 8; ++j) bfr[j] = *(const u32x4*)(sb + swz64(j * 16 + lrow, lg));
+      static_for<32>([&](auto m_) {
+        constexpr int m = decltype(m_)::value, h = m >> 4, i = (m >> 2) & 3, j = m & 3;
+        acc[h][i][j] = mfma_chunk<T>(af[i], bfr[h * 4 + j], acc[h][i][j]);  // D[px][co]
+        if constexpr (jt < 2 && (m & 7) == 7 && m < 24)
+          dma_w(std::integral_constant<int, 3 * jt + (m >> 3)>{}, vl, so, nx);
+      });
+    });
+    // pin that placement: per tap 0 / 1, 8 MFMAs then one piece three times, then the tap's last 8 MFMAs; tap 2's 32
+    // (0x008: MFMA, 0x020: vector-memory read; fragment reads and address arithmetic stay free)
+    static_assert(sizeof(T) == 2, "one MFMA per mfma_chunk");
 #pragma unroll
-      for (int h = 0; h < 2; ++h)
+    for (int t = 0; t < 2; ++t) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            acc[h][i][j] = mfma_chunk<T>(af[i], bfr[h * 4 + j], acc[h][i][j]);  // D[px][co]
+      for (int u = 0; u < 3; ++u) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
+        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+      }
+      __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
     }
+    __builtin_amdgcn_sched_group_barrier(0x008, 32, 0);
     SNRSE_STAMP(3 + 2 * (q & 15));
+    if (first && c + 1 < cbm) {
+      // the next chunk's halo, younger than this phase's pieces: the next phase top's vmcnt(HJ [+ 1]) retires the
+      // pieces and leaves these in flight for one more phase
+      vm_after_dma();
+      halo_load(c + 1);
+      gn_load(c + 1);
+      halo_inflight = true;
+    } else {
+      halo_inflight = false;
+    }
     if (last && c + 1 < cbm) {
       gn_publish();
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -1742,6 +1819,9 @@ __global__ __launch_bounds__(256, 2) void conv_halo5_kernel(ConvParams p) {
       vm_after_dma();
       halo_store(c + 1);
     }
+    soff += g == 1 ? soff_c : soff_g;  // phase q + 2 follows (c, 2) when g == 1
+    if (last) { g = 0; ++c; }
+    else ++g;
   }
   }
   SNRSE_STAMP(28);
