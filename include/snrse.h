@@ -21,6 +21,10 @@
  *     that takes SNRSE_BF16 takes SNRSE_F16 too), SNRSE_F32X3 = 4 (snrse_conv2d only: fp32 activations and output, weights
  *     pre-split into bf16 hi / lo halves, three bf16 MFMA products per K-tile -- the fast fp32
  *     parity mode).  Activations are NHWC: [B, F(=H), T(=W), C].
+ *   - Range: SNRSE_F16 holds magnitudes up to 65504 and every 16-bit store rounds to nearest, so a larger
+ *     value is stored as +-inf (SNRSE_BF16 has fp32's exponent range).  No entry checks this on its own;
+ *     snrse_range_stats reads a stored tensor back and reports its peak and its inf / NaN count per batch
+ *     row.  The Python host runs it once per enhancement and recomputes a damaged utterance in bf16.
  *   - Complex spectrograms are interleaved complex64 [B, F, T] (= the reference's
  *     [B, 1, F, T] tensors).
  */
@@ -258,6 +262,17 @@ int snrse_energy_ratios(const float* s_hat, const float* s, const float* n, int 
 
 /* norm_factor = max |y| per utterance (model.py:726): out[b] = max_i |sig[b][i]|. */
 int snrse_absmax(const float* sig, int B, int L, float* out, hipStream_t stream);
+
+/* Range statistics of a contiguous tensor [B][per] (dtype SNRSE_F32 / SNRSE_F16 / SNRSE_BF16; a complex64
+ * spectrogram is 2*per floats): peak[b] = max |v| over the FINITE elements of row b (0 when there is none),
+ * nonfinite[b] = number of inf / NaN elements of row b (saturating at INT_MAX).  accumulate == 0: overwrite
+ * peak / nonfinite; != 0: fold into their contents (max / saturating add), so a series of tensors can be folded
+ * into one slot without host work.  What the fp16 range guard (snrse/guard.py: one call per enhancement on the
+ * returned spectrogram) and the range probe (NCSNppHIP.range_report: every stored tensor of one evaluation)
+ * run; the GroupNorm statistics of the GEMM epilogues are taken before the 16-bit pack and stay finite when the
+ * stored value is +-inf.  csrc/range.hip. */
+int snrse_range_stats(const void* src, int B, long long per, int dtype, float* peak, int* nonfinite,
+                      int accumulate, hipStream_t stream);
 
 /* STFT (data_module.py:291-293 with spec_fwd 241-254 and pad_spec other.py:83-90):
  * sig [B][L] f32 -> out complex64 [B][256][Tpad], frames 1 + L/128 (the rest zero).

@@ -107,8 +107,7 @@ class NCSNpp(nn.Module):
             elif m.kind == "gn":
                 mods.append(nn.GroupNorm(min(m.cin // 4, 32), m.cin, eps=1e-6))
         self.all_modules = nn.ModuleList(mods)
-        self._hip_net = None
-        self._hip_key = None
+        self._hip_nets = {}  # compute_dtype -> (parameter key, executor): switching format does not repack
 
     # ---------------------------------------------------------------- device executor
     def _param_key(self):
@@ -116,16 +115,21 @@ class NCSNpp(nn.Module):
         return (self.compute_dtype, tuple(p._version for p in ps), tuple(p.data_ptr() for p in ps))
 
     def hip(self, device=None) -> _hip.NCSNppHIP:
-        """The packed device executor for the current parameters (re-packed on change)."""
+        """The packed device executor for the current parameters in the current compute_dtype (re-packed when the
+        parameters change).  One executor is kept per compute_dtype, so a model that alternates between two formats
+        (the range guard's fallback, ScoreModel.enhance) packs each once."""
         key = self._param_key()
-        if self._hip_net is None or self._hip_key != key:
+        held = self._hip_nets.get(self.compute_dtype)
+        if held is None or held[0] != key:
             dt = {"bf16": torch.bfloat16, torch.bfloat16: torch.bfloat16, "fp16": torch.float16,
                   torch.float16: torch.float16}.get(self.compute_dtype, torch.float32)
             gemm = "x3" if self.compute_dtype == "fp32x3" else "exact"  # split-bf16 fp32 GEMMs
             dev = device or (torch.device("cuda", torch.cuda.current_device()))
-            self._hip_net = _hip.NCSNppHIP(self.state_dict(), dtype=dt, device=dev, gemm=gemm, **self.cfg)
-            self._hip_key = key
-        return self._hip_net
+            for k in [k for k, (pk, _) in self._hip_nets.items() if pk[1:] != key[1:]]:
+                del self._hip_nets[k]  # executors of parameters that are gone
+            held = self._hip_nets[self.compute_dtype] = (
+                key, _hip.NCSNppHIP(self.state_dict(), dtype=dt, device=dev, gemm=gemm, **self.cfg))
+        return held[1]
 
     def forward(self, x, time_cond):
         """x: complex [B, 2, F, T] (x_t and y), time_cond: [B] -> complex [B, 1, F, T]."""

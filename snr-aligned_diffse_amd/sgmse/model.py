@@ -19,6 +19,7 @@ Defined behaviour where the reference cannot run:
 """
 from __future__ import annotations
 
+import contextlib
 import os
 import time
 import warnings
@@ -28,6 +29,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from snrse import guard as _guard
 from snrse import ops
 from snrse import sampler as _samp
 
@@ -272,8 +274,16 @@ class ScoreModel(nn.Module):
     # ------------------------------------------------------------------ enhance
     @torch.no_grad()
     def enhance(self, x, y, sampler_type="pc", predictor="reverse_diffusion", corrector="ald", N=30,
-                corrector_steps=1, snr=0.5, timeit=False, oracle=False, clean_rms=1, noise_rms=1, **kwargs):
-        """One-call enhancement of noisy speech y [1, L] (model.py:702-839) -> numpy [L]."""
+                corrector_steps=1, snr=0.5, timeit=False, oracle=False, clean_rms=1, noise_rms=1, range_guard="auto",
+                **kwargs):
+        """One-call enhancement of noisy speech y [1, L] (model.py:702-839) -> numpy [L].
+
+        range_guard (snrse.guard policies; "auto" = "fallback" when the backbone's compute_dtype is fp16, off
+        otherwise): the spectrogram is checked before the iSTFT; when fp16 could not hold the utterance (it is all
+        NaN then) the same branch runs again with the backbone in RANGE_FALLBACK ("bf16") under the torch RNG state
+        saved at entry, so the result is what a bf16 model returns under the same torch.manual_seed.  The fallback
+        is sticky: after the first hit this model runs the fallback format for the rest of the process and has
+        warned once, so a loop over the files of such a checkpoint does not pay twice per file."""
         start = time.time()
         # the checkpoint's data-module hparams pick the front / back end (_forward_transform(_stft(.)),
         # model.py:749, to_audio 612-613): fused exponent transform or raw, anything else raises
@@ -292,6 +302,51 @@ class ScoreModel(nn.Module):
         Tp = T_orig // 128 + 1
         Tp = Tp + (64 - Tp % 64) % 64
         noise_tape = kwargs.get("noise_tape")
+
+        def run():
+            return self._enhance_spec(yd, nf, T_orig, Tp, mode, dev, noise_tape, sampler_type, predictor, corrector, N,
+                                      corrector_steps, snr, oracle, clean_rms, noise_rms, kwargs)
+
+        fmt = self.dnn.compute_dtype
+        policy = _guard.resolve(range_guard, torch.float16 if fmt in ("fp16", torch.float16) else None)
+        if policy == "fallback" and self._range_fallback:
+            with self._compute_format(self.RANGE_FALLBACK):
+                sample, nfe, out_scale = run()
+            self.last_guard = {"flagged": [], "policy": policy, "fallback_dtype": self.RANGE_FALLBACK, "sticky": True}
+        else:
+            rng = (torch.get_rng_state(), torch.cuda.get_rng_state(dev)) if policy == "fallback" else None
+            sample, nfe, out_scale = run()
+            rows = _guard.flagged_rows(sample.contiguous()) if policy != "off" else []
+            if _guard.report(self, rows, policy, self.RANGE_FALLBACK, fmt):
+                self._range_fallback = True
+                torch.set_rng_state(rng[0])
+                torch.cuda.set_rng_state(rng[1], dev)
+                with self._compute_format(self.RANGE_FALLBACK):
+                    sample, nfe, out_scale = run()
+        x_hat = ops.istft(sample.contiguous(), T_orig, mode=mode, out_scale=out_scale.reshape(1).contiguous())
+        x_hat = x_hat[0].cpu().numpy()
+        if timeit:
+            rtf = (time.time() - start) / (len(x_hat) / 16000)
+            return x_hat, nfe, rtf
+        return x_hat
+
+    RANGE_FALLBACK = "bf16"   # compute_dtype enhance() falls back to when fp16 overflows
+    _range_fallback = False   # set by the first hit: this model then runs RANGE_FALLBACK
+    last_guard = None         # the latest enhance() call's guard record (snrse.guard.report)
+
+    @contextlib.contextmanager
+    def _compute_format(self, fmt):
+        """The backbone in another compute_dtype for the duration (it keeps one packed executor per format)."""
+        prev, self.dnn.compute_dtype = self.dnn.compute_dtype, fmt
+        try:
+            yield
+        finally:
+            self.dnn.compute_dtype = prev
+
+    def _enhance_spec(self, yd, nf, T_orig, Tp, mode, dev, noise_tape, sampler_type, predictor, corrector, N,
+                      corrector_steps, snr, oracle, clean_rms, noise_rms, kwargs):
+        """The network part of enhance(): normalised utterance -> (enhanced spectrogram [1, F, Tp], nfe, iSTFT
+        scale), in the backbone's current compute_dtype."""
         nfe = 1
         if self.snr_conditioned == "true":
             if self.model_type != "sebridge_v3":
@@ -337,12 +392,7 @@ class ScoreModel(nn.Module):
             else:
                 raise NotImplementedError(f"model_type={self.model_type!r} with snr_conditioned='false'")
             out_scale = div
-        x_hat = ops.istft(sample.contiguous(), T_orig, mode=mode, out_scale=out_scale.reshape(1).contiguous())
-        x_hat = x_hat[0].cpu().numpy()
-        if timeit:
-            rtf = (time.time() - start) / (len(x_hat) / 16000)
-            return x_hat, nfe, rtf
-        return x_hat
+        return sample, nfe, out_scale
 
 
 __all__ = ["ScoreModel", "t_30", "get_snr_model", "set_snr_model", "warnings"]

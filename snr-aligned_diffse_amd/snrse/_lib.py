@@ -40,6 +40,7 @@ SIGNATURES = {
     "snrse_axpby_noise": [_vp, _vp, _vp, _u64, _u64, _vp, _i, _i, _vp, _vp],
     "snrse_stft": [_vp, _i, _i, _vp, _f, _i, _i, _vp, _vp],
     "snrse_absmax": [_vp, _i, _i, _vp, _vp],
+    "snrse_range_stats": [_vp, _i, _ll, _i, _vp, _vp, _i, _vp],
     "snrse_energy_ratios": [_vp, _vp, _vp, _i, _i, _vp, _vp],
     "snrse_input_conv": [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp],
     "snrse_input_conv_x3": [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],

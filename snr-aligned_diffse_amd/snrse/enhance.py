@@ -17,6 +17,7 @@ import math
 import numpy as np
 import torch
 
+from . import guard as _guard
 from . import ops, sampler
 
 T_30 = (0.001 ** (1 / 7) + (np.arange(1, 31) - 1) / 29 * (1 - 0.001 ** (1 / 7))) ** 7  # model.py:22-23
@@ -56,10 +57,20 @@ class PCEnhancer:
     the other lane's full-resolution GEMMs.  stagger: lane k starts when lane k-1's first evaluation
     has reached the middle of the network (an event recorded between its down and up paths), so the
     lanes run half an evaluation apart instead of in phase.  The noise draws are the whole-batch ones
-    (LaneNoise), so the result equals the single-stream run."""
+    (LaneNoise), so the result equals the single-stream run.
+
+    guard (snrse.guard): "auto" (= "fallback" for an fp16 network, off otherwise), None / "off", "warn", "raise",
+    "fallback".  After the loop (the lanes joined) one range_stats launch and one B-element read-back look at the
+    returned spectrogram; an utterance the network's format could not hold is all NaN there.  "fallback" re-runs
+    those rows, run by run and on one stream, through net.fallback(fallback_dtype) with the draws the whole-batch
+    run took for them, and warns once per enhancer.  last_guard describes the latest call."""
 
     def __init__(self, net, sde: sampler.SDESpec, N=30, eps=0.03, snr=0.5, predictor="reverse_diffusion",
-                 corrector="ald", corrector_steps=1, score_mode=0, transform="exponent", streams=1, stagger=True):
+                 corrector="ald", corrector_steps=1, score_mode=0, transform="exponent", streams=1, stagger=True,
+                 guard="auto", fallback_dtype=torch.bfloat16):
+        _guard.resolve(guard, net.dtype)  # a bad policy fails here, not at the first call
+        self.guard, self.fallback_dtype = guard, fallback_dtype
+        self.last_guard = None
         self.net, self.sde, self.N, self.eps, self.snr = net, sde, N, eps, snr
         self.mode = transform_mode(transform)
         self.predictor, self.corrector, self.corrector_steps = predictor, corrector, corrector_steps
@@ -68,8 +79,8 @@ class PCEnhancer:
         self.stagger = bool(stagger)
         self._lane_streams = {}
 
-    def _iter(self, Y, noise):
-        net = self.net
+    def _iter(self, Y, noise, net=None):
+        net = net or self.net
 
         def step(x, tv, coef, z, seed, off):
             pyr = net.pyramid(x, Y, tv)
@@ -84,17 +95,31 @@ class PCEnhancer:
                                       predictor=self.predictor, corrector=self.corrector,
                                       corrector_steps=self.corrector_steps, noise=noise, score_tensor=score_tensor)
 
+    @staticmethod
+    def _drain(it):
+        while True:
+            try:
+                next(it)
+            except StopIteration as e:
+                return e.value
+
     def sample(self, Y, noise: sampler.NoiseSource | None = None):
-        B = Y.shape[0]
+        policy = _guard.resolve(self.guard, self.net.dtype)
         noise = noise or sampler.NoiseSource()
+        snap = _guard.snapshot(noise) if policy == "fallback" else None
+        x, nfe = self._sample(Y, noise)
+        rows = _guard.flagged_rows(x) if policy != "off" else []
+        if _guard.report(self, rows, policy, self.fallback_dtype, self.net.dtype):
+            fb = _guard.fallback_net(self.net, self.fallback_dtype)
+            for a, b, lane in _guard.run_noise(snap, rows, Y.shape[0]):
+                x[a:b] = self._drain(self._iter(Y[a:b].contiguous(), lane, net=fb))[0]
+        return x, nfe
+
+    def _sample(self, Y, noise):
+        B = Y.shape[0]
         nl = min(self.streams, B)
         if nl <= 1:
-            it = self._iter(Y, noise)
-            while True:
-                try:
-                    next(it)
-                except StopIteration as e:
-                    return e.value
+            return self._drain(self._iter(Y, noise))
         cur = torch.cuda.current_stream(Y.device)
         bounds = [(B * h // nl, B * (h + 1) // nl) for h in range(nl)]
         lanes, lane_noise = [], []
@@ -147,9 +172,14 @@ class SNRAlignedEnhancer:
     -> Y = spec_fwd(STFT(y / (max|y| normfac))) -> X_T = Y + sigma_max t_hat Z -> one
     preconditioned NCSN++ evaluation at t_hat (c_skip x + c_out dnn, score mode 1) -> iSTFT x
     max|y| normfac.  The per-utterance scalars (t_hat, normfac) are host float64 as in the
-    reference (one B-element copy).  Returns (x_hat [B, L], t_hat numpy [B])."""
+    reference (one B-element copy).  Returns (x_hat [B, L], t_hat numpy [B]).  guard / fallback_dtype: the range
+    guard of PCEnhancer, checked on the network's output before the iSTFT."""
 
-    def __init__(self, net, snr_fn=None, fixed_snr=0.17783, sigma_max=0.5, transform="exponent"):
+    def __init__(self, net, snr_fn=None, fixed_snr=0.17783, sigma_max=0.5, transform="exponent", guard="auto",
+                 fallback_dtype=torch.bfloat16):
+        _guard.resolve(guard, net.dtype)
+        self.guard, self.fallback_dtype = guard, fallback_dtype
+        self.last_guard = None
         self.net, self.snr_fn = net, snr_fn
         self.mode = transform_mode(transform)
         self.fixed_snr, self.sigma_max = float(fixed_snr), float(sigma_max)
@@ -170,4 +200,11 @@ class SNRAlignedEnhancer:
         X_T = ops.axpby_noise(coef.to(Y.device), y=Y, noise=noise, seed=seed)
         tv = torch.from_numpy(t_hat).to(Y.device, torch.float32)
         sample = self.net.score(X_T, Y, tv, 1)
+        # range guard (PCEnhancer): X_T does not depend on the network's format, so the flagged rows are one more
+        # evaluation of the fallback executor on the same X_T
+        policy = _guard.resolve(self.guard, self.net.dtype)
+        rows = _guard.flagged_rows(sample) if policy != "off" else []
+        if _guard.report(self, rows, policy, self.fallback_dtype, self.net.dtype):
+            fb = _guard.fallback_net(self.net, self.fallback_dtype)
+            sample[rows] = fb.score(X_T[rows].contiguous(), Y[rows].contiguous(), tv[rows].contiguous(), 1)
         return ops.istft(sample.contiguous(), L, mode=self.mode, out_scale=div.contiguous()), t_hat

@@ -112,6 +112,28 @@ def _pack1x1(w, dt, npad=None):
     return _pack3x3(w, dt, npad)
 
 
+class RangeProbe:
+    """Slots of NCSNppHIP.range_report: one (peak [B], nonfinite [B]) row per tensor name, in first-seen order,
+    zeroed once up front; add() is one ops.range_stats launch folding into the tensor's row."""
+
+    CAP = 512  # rows allocated (the shipped plan stores ~270 tensors per evaluation)
+
+    def __init__(self, B, device):
+        self.names = {}
+        self.peak = torch.zeros(self.CAP, B, device=device, dtype=torch.float32)
+        self.nonfinite = torch.zeros(self.CAP, B, device=device, dtype=torch.int32)
+
+    def add(self, name, t):
+        row = self.names.setdefault(name, len(self.names))
+        if row >= self.CAP:
+            raise RuntimeError(f"snrse: range probe holds {self.CAP} tensors")
+        ops.range_stats(t, self.peak[row], self.nonfinite[row], accumulate=True)
+
+    def result(self):
+        peak, nonfinite = self.peak.cpu(), self.nonfinite.cpu()
+        return [(name, peak[row], nonfinite[row]) for name, row in self.names.items()]
+
+
 class NCSNppHIP:
     """Device-resident packed weights + the forward executor."""
 
@@ -128,6 +150,9 @@ class NCSNppHIP:
         self.dtype = dtype
         self.gemm = gemm
         self.device = torch.device(device)
+        self._src = (sd, cfg)   # the weights and configuration this executor was packed from (references): fallback()
+        self._fallbacks = {}    # (dtype, gemm) -> executor of the same weights in another format
+        self._probe = None      # RangeProbe of range_report(), None outside it
         self._arena = None  # ops.StatsArena of the GroupNorm statistics, one fill per evaluation
         self._arenas = {}   # one arena per launch stream (the two-stream sampler runs evaluations concurrently)
         self.mid_hook = None  # callable run once between the down and the up path of the next evaluation
@@ -201,6 +226,43 @@ class NCSNppHIP:
                     e["wqkv"] = ops.split_weight(e["wqkv"])
                     e["w3"] = ops.split_weight(e["w3"])
 
+    # ------------------------------------------------------------------ other formats, range probe
+    def fallback(self, dtype=torch.bfloat16, gemm="exact"):
+        """An executor of the same weights in another format (bf16 by default; torch.float32 with gemm="x3" for the
+        split-bf16 fp32 mode), packed on first use from the ORIGINAL weights -- converting this executor's 16-bit
+        packing would round them twice -- and kept: the range guard (snrse.guard) recomputes with it the utterances
+        that left this executor's range."""
+        key = (dtype, gemm)
+        if key == (self.dtype, self.gemm):
+            return self
+        fb = self._fallbacks.get(key)
+        if fb is None:
+            sd, cfg = self._src
+            fb = self._fallbacks[key] = NCSNppHIP(sd, dtype=dtype, device=self.device, gemm=gemm, **cfg)
+        return fb
+
+    def _note(self, name, t):
+        """Range-probe hook after a tensor the executor stored: a None check outside range_report()."""
+        if self._probe is not None:
+            self._probe.add(name, t)
+        return t
+
+    def range_report(self, x, y, t):
+        """One evaluation (pyramid) with the range probe installed: after every tensor the executor stores -- the
+        input conv output, each ResBlock's Conv_0 / Conv_1 output, the attention blocks' QKV, core and NIN_3 outputs,
+        the gn_apply / gn_resample / fir outputs and the pyramid heads -- ops.range_stats folds that tensor into its
+        slot (one extra read per tensor; no host synchronisation until the end).  Returns, in execution order,
+        [(name, peak [B] f32, nonfinite [B] i32)] (host tensors); names start with the plan index of the module
+        ("4.rb.conv1": Conv_1 output, i.e. the block output, of all_modules.4).  On a bf16 or fp32 executor a peak
+        above 65504 with nonfinite == 0 shows that fp16 would overflow there, without producing a NaN first."""
+        probe = RangeProbe(x.shape[0], x.device)
+        self._probe = probe
+        try:
+            self.pyramid(x, y, t)
+        finally:
+            self._probe = None
+        return probe.result()
+
     # ------------------------------------------------------------------ blocks
     # Every activation travels with its per-channel GroupNorm statistics, produced by the
     # epilogue of the GEMM that wrote it, so no separate statistics pass is needed.
@@ -216,6 +278,7 @@ class NCSNppHIP:
         Where the halo GEMM applies (16-bit, 3x3, H%4 == 0, W%64 == 0) GroupNorm+SiLU is fused
         into the GEMM's halo load; otherwise it is one gn_apply pass (with the FIR for up/down)."""
         e = self.mw[m.idx]
+        note, p = self._note, f"{m.idx}.rb"
         mode = "up" if m.up else ("down" if m.down else "none")
         (t0, s0), (t1, s1) = x0, (x1 if x1 is not None else (None, None))
         B, H, W, _ = t0.shape
@@ -229,33 +292,43 @@ class NCSNppHIP:
             # one LDS-tiled pass: SiLU(GN(x)) resampled for Conv_0 and the raw FIR of x for Conv_2
             gn0 = ops.gn_scale_shift(s0, e["gn0_g"], e["gn0_b"], H * W)
             a0, xs_raw = ops.gn_resample(t0, *gn0, act=True, mode=mode, want_raw="w2" in e)
+            note(p + ".gn0", a0)
+            if xs_raw is not None:
+                note(p + ".fir", xs_raw)
             h, hs_ = self._conv(a0, e["w0"], 3, m.cout, bias=e["b0"], temb=dense, temb_off=e["temb_off"])
         else:
-            a0 = ops.gn_apply(t0, t1, s0, e["gn0_g"], e["gn0_b"], act=True, mode=mode, sums1=s1)
+            a0 = note(p + ".gn0", ops.gn_apply(t0, t1, s0, e["gn0_g"], e["gn0_b"], act=True, mode=mode, sums1=s1))
             h, hs_ = self._conv(a0, e["w0"], 3, m.cout, bias=e["b0"], temb=dense, temb_off=e["temb_off"])
+        note(p + ".conv0", h)
         Hh, Wh = h.shape[1], h.shape[2]
         if fused(h, 3, m.cout):
             src, gn1 = h, ops.gn_scale_shift(hs_, e["gn1_g"], e["gn1_b"], Hh * Wh)
         else:
-            src, gn1 = ops.gn_apply(h, None, hs_, e["gn1_g"], e["gn1_b"], act=True), None
+            src, gn1 = note(p + ".gn1", ops.gn_apply(h, None, hs_, e["gn1_g"], e["gn1_b"], act=True)), None
         if "w2" in e:
             if mode != "none":
-                xs0, xs1 = (ops.fir(t0, mode) if xs_raw is None else xs_raw), None
+                xs0, xs1 = (note(p + ".fir", ops.fir(t0, mode)) if xs_raw is None else xs_raw), None
             else:
                 xs0, xs1 = t0, t1
-            return self._conv(src, e["w1"], 3, m.cout, gn=gn1, bias=e["b1"], sc=xs0, sc1=xs1, sc_wgt=e["w2"],
-                              out_scale=INV_SQRT2, comb=comb, comb_w=comb_w, comb_b=comb_b)
-        assert t1 is None
-        return self._conv(src, e["w1"], 3, m.cout, gn=gn1, bias=e["b1"], res=t0, out_scale=INV_SQRT2,
-                          comb=comb, comb_w=comb_w, comb_b=comb_b)
+            out = self._conv(src, e["w1"], 3, m.cout, gn=gn1, bias=e["b1"], sc=xs0, sc1=xs1, sc_wgt=e["w2"],
+                             out_scale=INV_SQRT2, comb=comb, comb_w=comb_w, comb_b=comb_b)
+        else:
+            assert t1 is None
+            out = self._conv(src, e["w1"], 3, m.cout, gn=gn1, bias=e["b1"], res=t0, out_scale=INV_SQRT2,
+                             comb=comb, comb_w=comb_w, comb_b=comb_b)
+        note(p + ".conv1", out[0])
+        return out
 
     def _attn(self, m, x):
         e = self.mw[m.idx]
         t, s = x
-        a = ops.gn_apply(t, None, s, e["gn_g"], e["gn_b"], act=False)
+        note, p = self._note, f"{m.idx}.attn"
+        a = note(p + ".gn", ops.gn_apply(t, None, s, e["gn_g"], e["gn_b"], act=False))
         qkv, _ = self._conv(a, e["wqkv"], 1, 3 * m.cout, bias=e["bqkv"], want_stats=False)
-        o = ops.attention(qkv, m.cout, split=self.gemm == "x3")
-        return self._conv(o, e["w3"], 1, m.cout, bias=e["b3"], res=t, out_scale=INV_SQRT2)
+        o = note(p + ".out", ops.attention(note(p + ".qkv", qkv), m.cout, split=self.gemm == "x3"))
+        out = self._conv(o, e["w3"], 1, m.cout, bias=e["b3"], res=t, out_scale=INV_SQRT2)
+        note(p + ".nin3", out[0])
+        return out
 
     def _pyramid_head(self, gn_m, conv_m, h, pyr_up):
         g = self.mw[gn_m.idx]
@@ -263,9 +336,10 @@ class NCSNppHIP:
         t, s = h
         if ops.head_ok(t, split=self.gemm == "x3"):  # GroupNorm+SiLU fused into the head conv's halo load
             gn = ops.gn_scale_shift(s, g["g"], g["b"], t.shape[1] * t.shape[2])
-            return ops.conv2d(t, c["w"], 3, 4, bias=c["b"], res=pyr_up, out_f32=True, gn=gn)
-        a = ops.gn_apply(t, None, s, g["g"], g["b"], act=True)
-        return ops.conv2d(a, c["w"], 3, 4, bias=c["b"], res=pyr_up, out_f32=True)
+            return self._note(f"{conv_m.idx}.head",
+                              ops.conv2d(t, c["w"], 3, 4, bias=c["b"], res=pyr_up, out_f32=True, gn=gn))
+        a = self._note(f"{gn_m.idx}.gn", ops.gn_apply(t, None, s, g["g"], g["b"], act=True))
+        return self._note(f"{conv_m.idx}.head", ops.conv2d(a, c["w"], 3, 4, bias=c["b"], res=pyr_up, out_f32=True))
 
     # ------------------------------------------------------------------ forward
     def temb(self, t):
@@ -296,6 +370,7 @@ class NCSNppHIP:
         else:
             col, pyr_in = ops.input_pack(x, y, self.dtype)
             h = self._conv(col, W["in_w"], 1, 128, bias=W["in_b"])
+        self._note("3.conv", h[0])
         hs = [h]
         plan = self.plan
         i = 4
@@ -310,7 +385,7 @@ class NCSNppHIP:
                 hs.append(h)
             if lvl != nres - 1:
                 rb, cmb = plan[i], plan[i + 1]
-                pyr_in = ops.fir(pyr_in, "down")
+                pyr_in = self._note(f"{cmb.idx}.combine.fir", ops.fir(pyr_in, "down"))
                 ce = self.mw[cmb.idx]
                 h = self._resblock(rb, hs[-1], None, dense, comb=pyr_in, comb_w=ce["w"], comb_b=ce["b"])
                 i += 2
@@ -330,7 +405,7 @@ class NCSNppHIP:
             if plan[i].kind == "attn":
                 h = self._attn(plan[i], h)
                 i += 1
-            pyr_up = None if pyr is None else ops.fir(pyr, "up")
+            pyr_up = None if pyr is None else self._note(f"{plan[i + 1].idx}.head.fir", ops.fir(pyr, "up"))
             pyr = self._pyramid_head(plan[i], plan[i + 1], h, pyr_up)
             i += 2
             if lvl != 0:

@@ -570,7 +570,10 @@ def input_pack(x, y, dtype):
 
 def score_update(pyr, out_w, out_b, t, score_mode, x, y=None, coef=None, noise=None, seed=0, offset=0,
                  want_score=False, x_out=None, xmean_out=None):
-    """Output head + score + optional SDE step.  Returns (x_out, x_mean, score)."""
+    """Output head + score + optional SDE step.  Returns (x_out, x_mean, score).  pyr: float32, or bfloat16 (the
+    library reads any other 16-bit pattern as bf16, so a float16 pyramid is refused here)."""
+    if pyr.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"snrse: score_update takes a float32 or bfloat16 pyramid, got {pyr.dtype}")
     _dev(pyr, out_w, out_b, t, x, y, coef, noise)
     B = x.shape[0]
     HW = x.shape[-2] * x.shape[-1]
@@ -630,6 +633,30 @@ def absmax(sig):
     out = torch.empty(B, device=sig.device, dtype=torch.float32)
     _lib.call("snrse_absmax", sig.data_ptr(), B, L, out.data_ptr(), _stream())
     return out
+
+
+def range_stats(t, peak=None, nonfinite=None, accumulate=False):
+    """Range statistics of a contiguous device tensor whose leading dimension counts the rows (float32, float16,
+    bfloat16, or complex64 read as interleaved floats): (peak [B] f32 = max |v| over the finite elements of each
+    row, nonfinite [B] i32 = its number of inf / NaN elements) -- snrse_range_stats.  peak / nonfinite: slots to
+    write; accumulate=True folds into their contents (max / saturating add) instead of overwriting them."""
+    _dev(t, peak, nonfinite)
+    if t.dim() < 1 or t.numel() == 0:
+        raise ValueError("snrse: range_stats needs a non-empty tensor with a leading row dimension")
+    B = t.shape[0]
+    if t.dtype == torch.complex64:
+        dt, per = F32, 2 * (t.numel() // B)
+    else:
+        dt, per = code(t.dtype), t.numel() // B
+    if (peak is None or nonfinite is None) and accumulate:
+        raise ValueError("snrse: range_stats(accumulate=True) folds into given peak / nonfinite slots")
+    peak = torch.empty(B, device=t.device, dtype=torch.float32) if peak is None else peak
+    nonfinite = torch.empty(B, device=t.device, dtype=torch.int32) if nonfinite is None else nonfinite
+    if (peak.dtype, nonfinite.dtype) != (torch.float32, torch.int32) or peak.numel() != B or nonfinite.numel() != B:
+        raise TypeError("snrse: range_stats slots are peak [B] float32 and nonfinite [B] int32")
+    _lib.call("snrse_range_stats", t.data_ptr(), B, per, dt, peak.data_ptr(), nonfinite.data_ptr(),
+              int(bool(accumulate)), _stream())
+    return peak, nonfinite
 
 
 def stft(sig, in_scale=1.0, tpad=None, mode=1, in_div=None):
