@@ -300,6 +300,30 @@ int snrse_snrnet(const void* spec, int B, int T, const float* w5, const float* b
                  float* out, hipStream_t stream);
 size_t snrse_snrnet_workspace(int B, int T);
 
+/* ---- Training of the SNR estimator (snr_estimator.py:81-116 around SNRNet; csrc/snrnet_train.hip), f32.
+ * T % 16 == 0 and T >= 32 (one chunk makes the unbiased std over the chunks, and the loss, NaN). */
+
+/* Batch perturbation (snr_estimator.py:93-98) on interleaved complex64 [B][per]:
+ * out = (x + (y - x) 0.56234 SNR) 2.040166 / sqrt(1 + SNR^2), SNR = gt[b] / (1 - gt[b]). */
+int snrse_snr_perturb(const void* x, const void* y, const float* gt, int B, long long per, void* out,
+                      hipStream_t stream);
+/* snrse_snrnet that also saves what the backward needs (pool winners, LSTM gates and cell states, the head's
+ * argmin / argmax) in tws, snrse_snrnet_train_workspace(B, T) bytes kept by the caller until the backward. */
+int snrse_snrnet_train_fwd(const void* spec, int B, int T, const float* w5, const float* b5, const float* w3,
+                           const float* b3, const float* wt1, const float* wt2, const float* wt3, const float* wt4,
+                           const float* bt1, const float* bt2, const float* bt3, const float* bt4, const float* wih,
+                           const float* bsum, const float* whh, const float* fcw, const float* fcb, void* tws,
+                           float* out, hipStream_t stream);
+size_t snrse_snrnet_train_workspace(int B, int T);
+/* est [B]: the forward's output; dest [B]: d loss / d est.  Gradients in the layout of the packed weights
+ * (dwih / dwhh [2][512][128]; dbsum [2][512] is the gradient of bias_ih and of bias_hh alike). */
+int snrse_snrnet_backward(const void* spec, int B, int T, const float* est, const float* dest, const float* w3,
+                          const float* wt1, const float* wt2, const float* wt3, const float* wt4, const float* wih,
+                          const float* whh, const float* fcw, void* tws, float* dw5, float* db5, float* dw3,
+                          float* db3, float* dwt1, float* dwt2, float* dwt3, float* dwt4, float* dbt1, float* dbt2,
+                          float* dbt3, float* dbt4, float* dwih, float* dbsum, float* dwhh, float* dfcw, float* dfcb,
+                          hipStream_t stream);
+
 /* ---- Consistency-training step (ScoreModel._step, model.py:361-390, with the
  * backward pass PyTorch Lightning runs through loss.backward() and the Adam / torch_ema updates of
  * model.py:99-106).  All f32, NHWC activations; csrc/train.hip. */

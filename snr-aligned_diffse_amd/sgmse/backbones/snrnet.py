@@ -55,3 +55,17 @@ class SNRNet(nn.Module):
             raise RuntimeError("SNRNet.forward: HIP device tensors required (no CPU fallback)")
         spec = torch.complex(x[:, 0].float(), x[:, 1].float()).contiguous()
         return self.forward_complex(spec)
+
+    def forward_train(self, x):
+        """The differentiable forward (snrse.snr_train): x [B, 2, 256, T] real / imag planes, or the complex
+        STFT [B, 256, T] / [B, 1, 256, T]; T % 16 == 0, T >= 32 -> est [B, 1] whose backward() fills the
+        .grad of all 22 parameters on the HIP backward kernels.  `forward` stays the inference path."""
+        from snrse import snr_train
+        snr_train.check_frames(x.shape[-1])
+        if not x.is_cuda:
+            raise RuntimeError("SNRNet.forward_train: HIP device tensors required (no CPU fallback)")
+        if x.is_complex():
+            spec = x.reshape(x.shape[0], x.shape[-2], x.shape[-1])
+        else:
+            spec = torch.complex(x[:, 0].float(), x[:, 1].float())
+        return snr_train.snrnet_train(spec.contiguous(), self.state_dict(keep_vars=True))

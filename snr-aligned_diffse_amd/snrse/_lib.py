@@ -73,9 +73,14 @@ SIGNATURES = {
     "snrse_ct_perturb": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp],
     "snrse_ct_loss": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp],
     "snrse_adam_ema": [_vp, _vp, _vp, _i, _f, _f, _f, _f, _f, _f, _f, _vp],
+    # SNR-estimator training (csrc/snrnet_train.hip)
+    "snrse_snr_perturb": [_vp, _vp, _vp, _i, _ll, _vp, _vp],
+    "snrse_snrnet_train_fwd": [_vp, _i, _i] + [_vp] * 17 + [_vp, _vp, _vp],
+    "snrse_snrnet_backward": [_vp, _i, _i, _vp, _vp] + [_vp] * 8 + [_vp] + [_vp] * 17 + [_vp],
 }
 HOUSEKEEPING = {"snrse_abi_version": ([], _i), "snrse_build_id": ([], C.c_char_p), "snrse_error_string": ([_i], C.c_char_p),
                 "snrse_device_name": ([C.c_char_p, _i], _i), "snrse_snrnet_workspace": ([_i, _i], C.c_size_t),
+                "snrse_snrnet_train_workspace": ([_i, _i], C.c_size_t),
                 "snrse_ctx_create": ([], _vp), "snrse_ctx_destroy": ([_vp], None)}
 
 _lib = None

@@ -480,14 +480,56 @@ def gen_train_step():
     save("train_step.npz", **out)
 
 
+SNR_TRAIN_SHAPE = (2, 256, 64)  # B, F, T of the SNR-estimator training-step golden
+SNR_TRAIN_GT = [0.3, 0.7]       # gt (torch.rand(B) * 0.999 in the reference): SNR = gt / (1 - gt)
+SNR_TRAIN_FULL_MAX = 10000      # gradients up to this many elements are stored whole, TRAIN_HEAD elements of the others
+
+
+def gen_snr_train_step():
+    """The SNR estimator's training step: snr_estimator.py:93-98 (perturbation), 105-109 (view_as_real /
+    permute, forward) and 81-83 (mse loss), restated around the REFERENCE SNRNet module (formula weights;
+    SNRModel itself needs pytorch_lightning) and differentiated by torch autograd on the CPU.  Stored: the loss,
+    est, every gradient's (sum, sum of squares, max |g|), the full gradient of the tensors with at most
+    SNR_TRAIN_FULL_MAX elements and the first TRAIN_HEAD elements of the others."""
+    net = SNRNet().train()
+    load_formula(net, "snrnet.")
+    B, Fq, T = SNR_TRAIN_SHAPE
+    x = fnormal("golden.snrtrain.x", (B, 1, Fq, T), complex_=True) * 0.4
+    y = fnormal("golden.snrtrain.n", (B, 1, Fq, T), complex_=True) * 0.4 + x
+    gt = torch.tensor(SNR_TRAIN_GT, dtype=torch.float32)
+    SNR = (gt / (1 - gt)).unsqueeze(1).unsqueeze(2).unsqueeze(3)
+    y = x + (y - x) * 0.56234 * SNR
+    normfac_ = (2.040166) * (0.240253 + 0.759747 * 1 ** 2) ** 0.5 / ((1 + (SNR / 1) ** 2) ** 0.5)
+    y = y * normfac_
+    yp = y
+    y = torch.view_as_real(y).permute(0, 4, 2, 3, 1).squeeze(4)
+    est = net(y)
+    loss = torch.nn.functional.mse_loss(gt, est.squeeze(1))
+    loss.backward()
+    names = [k for k, _ in net.named_parameters()]
+    g = {k: p.grad.detach().double() for k, p in net.named_parameters()}
+    full = [k for k in names if g[k].numel() <= SNR_TRAIN_FULL_MAX]
+    out = {"gt": t2n(gt), "loss": np.float64(loss.item()), "est": t2n(est), "names": np.asarray(names),
+           "full_keys": np.asarray(full), "head": np.int64(TRAIN_HEAD),
+           "perturbed_head": t2n(torch.view_as_real(yp.reshape(B, -1)[:, :64])),
+           "gsum": np.asarray([float(g[k].sum()) for k in names]),
+           "gsq": np.asarray([float((g[k] ** 2).sum()) for k in names]),
+           "gmax": np.asarray([float(g[k].abs().max()) for k in names]),
+           "heads": np.concatenate([t2n(g[k].float()).reshape(-1)[:TRAIN_HEAD] for k in names if k not in full])}
+    for k in full:
+        out[f"full__{k}"] = t2n(g[k].float())
+    save("snr_train_step.npz", **out)
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     which = sys.argv[1:] or ["keys", "fir", "blocks", "attn", "ncsnpp", "sde", "pc_ouve",
-                             "pc_variants", "stft", "snrnet", "sebridge", "c4", "train"]
+                             "pc_variants", "stft", "snrnet", "sebridge", "c4", "train", "snr_train"]
     table = {"keys": gen_keys, "fir": gen_fir, "blocks": gen_blocks, "attn": gen_attn,
              "ncsnpp": gen_ncsnpp, "sde": gen_sde, "pc_ouve": gen_pc_ouve,
              "pc_variants": gen_pc_variants, "stft": gen_stft, "snrnet": gen_snrnet,
-             "sebridge": gen_sebridge_enhance, "c4": gen_snr_enhance, "train": gen_train_step}
+             "sebridge": gen_sebridge_enhance, "c4": gen_snr_enhance, "train": gen_train_step,
+             "snr_train": gen_snr_train_step}
     for w in which:
         torch.manual_seed(0)
         table[w]()
