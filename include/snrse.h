@@ -254,6 +254,20 @@ int snrse_sde_update(const void* x, const void* y, const void* score, const void
 int snrse_axpby_noise(const void* x, const void* y, const void* noise, uint64_t seed, uint64_t offset,
                       const float* coef, int B, int HW, void* out, hipStream_t stream);
 
+/* Row-seeded forms of the three entries above: the draw of element e of batch row b is
+ * Philox4x32-10(row_seed[b], draw * HW + e), exactly what the entry above draws for a [1][HW] batch with
+ * seed = row_seed[b], offset = draw * HW -- so an utterance's noise depends on its own seed and the draw index
+ * only, not on the batch it shares or its row in it.  row_seed [B] on the device; noise != NULL overrides it. */
+int snrse_score_update_rs(const void* pyr, int pyr_f32, const float* out_w, const float* out_b,
+                          const float* t, int score_mode, int B, int HW, const void* x, const void* y,
+                          const void* noise, const uint64_t* row_seed, uint64_t draw, const float* coef,
+                          void* x_out, void* xmean_out, void* score_out, hipStream_t stream);
+int snrse_sde_update_rs(const void* x, const void* y, const void* score, const void* noise,
+                        const uint64_t* row_seed, uint64_t draw, const float* coef, int B, int HW, void* x_out,
+                        void* xmean_out, hipStream_t stream);
+int snrse_axpby_noise_rs(const void* x, const void* y, const void* noise, const uint64_t* row_seed,
+                         uint64_t draw, const float* coef, int B, int HW, void* out, hipStream_t stream);
+
 /* Evaluation metrics (eval.py:144-157 -> utils.py:10-35 energy_ratios, sgmse/util/other.py:71-75
  * si_sdr), batched: s_hat, s, n [B][L] f32 (n may be NULL) -> out [B][3] f64 = (SI-SDR, SI-SIR,
  * SI-SAR) in dB from six fp64 dot products per utterance; SI-SIR / SI-SAR are NaN without n. */
@@ -262,6 +276,17 @@ int snrse_energy_ratios(const float* s_hat, const float* s, const float* n, int 
 
 /* norm_factor = max |y| per utterance (model.py:726): out[b] = max_i |sig[b][i]|. */
 int snrse_absmax(const float* sig, int B, int L, float* out, hipStream_t stream);
+
+/* Ragged batches: utterances of different lengths in one [B][Lstride] f32 buffer with lengths [B] int32 on the
+ * device; row b is valid on [0, L_b) and nothing at or past L_b is read into a result.  The metrics' dot
+ * products and the maximum run over [0, L_b).  The STFT reflects each row at its own L_b, writes its
+ * T_b = 1 + L_b / 128 frames and zeroes frames [T_b, Tpad); the lengths live on the device, so the CALLER checks
+ * 255 < L_b <= Lstride and T_b <= Tpad before the call (snrse.ops.stft raises for them). */
+int snrse_energy_ratios_ragged(const float* s_hat, const float* s, const float* n, const int* lengths, int B,
+                               int Lstride, double* out, hipStream_t stream);
+int snrse_absmax_ragged(const float* sig, const int* lengths, int B, int Lstride, float* out, hipStream_t stream);
+int snrse_stft_ragged(const float* sig, const int* lengths, int B, int Lstride, const float* in_div,
+                      float in_scale, int Tpad, int mode, void* out, hipStream_t stream);
 
 /* Range statistics of a contiguous tensor [B][per] (dtype SNRSE_F32 / SNRSE_F16 / SNRSE_BF16; a complex64
  * spectrogram is 2*per floats): peak[b] = max |v| over the FINITE elements of row b (0 when there is none),

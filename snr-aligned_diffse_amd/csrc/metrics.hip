@@ -15,12 +15,14 @@ namespace {
 
 constexpr int MT = 512;
 
+// Rows are `stride` samples apart; ragged (lengths [B]): the dot products of row b run over [0, L_b) only.
 __global__ __launch_bounds__(MT) void energy_ratios_kernel(const float* s_hat, const float* s, const float* n, int L,
-                                                           double* out) {
+                                                           int stride, const int* lengths, double* out) {
   const int b = blockIdx.x;
-  const float* ph = s_hat + (size_t)b * L;
-  const float* ps = s + (size_t)b * L;
-  const float* pn = n ? n + (size_t)b * L : nullptr;
+  if (lengths) L = min(max(lengths[b], 0), stride);
+  const float* ph = s_hat + (size_t)b * stride;
+  const float* ps = s + (size_t)b * stride;
+  const float* pn = n ? n + (size_t)b * stride : nullptr;
   double acc[6] = {0, 0, 0, 0, 0, 0};  // ss, nn, hh, hs, hn, sn
   for (int i = threadIdx.x; i < L; i += MT) {
     const double h = ph[i], x = ps[i], z = pn ? (double)pn[i] : 0.0;
@@ -65,6 +67,15 @@ __global__ __launch_bounds__(MT) void energy_ratios_kernel(const float* s_hat, c
 extern "C" int snrse_energy_ratios(const float* s_hat, const float* s, const float* n, int B, int L, double* out,
                                    hipStream_t stream) {
   if (B <= 0 || L <= 0 || !s_hat || !s || !out) return SNRSE_EINVAL;
-  hipLaunchKernelGGL(energy_ratios_kernel, dim3(B), dim3(MT), 0, stream, s_hat, s, n, L, out);
+  hipLaunchKernelGGL(energy_ratios_kernel, dim3(B), dim3(MT), 0, stream, s_hat, s, n, L, L, (const int*)nullptr,
+                     out);
+  return (int)hipGetLastError();
+}
+
+extern "C" int snrse_energy_ratios_ragged(const float* s_hat, const float* s, const float* n, const int* lengths,
+                                          int B, int Lstride, double* out, hipStream_t stream) {
+  if (B <= 0 || Lstride <= 0 || !s_hat || !s || !lengths || !out) return SNRSE_EINVAL;
+  hipLaunchKernelGGL(energy_ratios_kernel, dim3(B), dim3(MT), 0, stream, s_hat, s, n, Lstride, Lstride, lengths,
+                     out);
   return (int)hipGetLastError();
 }

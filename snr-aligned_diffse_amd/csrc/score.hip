@@ -695,6 +695,17 @@ SNRSE_DEV float2 cnormal(uint64_t seed, uint64_t ctr) {
   return make_float2(rad * cs * 0.70710678118654752f, rad * sn * 0.70710678118654752f);
 }
 
+// Draw of element p (row b of a [B, HW] batch).  Batch-keyed (row_seed == nullptr): Philox(seed, offset + p), the
+// counter runs over the whole batch.  Row-seeded: Philox(row_seed[b], offset * HW + e) with e the element's index
+// inside its row and `offset` the draw index -- what the batch-keyed form draws for a [1, HW] batch with
+// seed = row_seed[b], offset = draw * HW, so a row's numbers do not depend on its batch or its place in it.  The
+// choice is uniform over a wave (HW is a multiple of 64 on the network's shapes), one Philox call either way.
+SNRSE_DEV float2 draw_normal(const uint64_t* row_seed, uint64_t seed, uint64_t offset, int p, int b, int HW) {
+  const uint64_t key = row_seed ? row_seed[b] : seed;
+  const uint64_t ctr = row_seed ? offset * (uint64_t)HW + (uint64_t)(p - b * HW) : offset + (uint64_t)p;
+  return cnormal(key, ctr);
+}
+
 struct StepCoef {
   float a, by, c, s;  // x_mean = a x + by y + c score ; x = x_mean + s z
 };
@@ -702,8 +713,8 @@ struct StepCoef {
 template <typename TP>
 __global__ __launch_bounds__(256) void score_update_kernel(
     const TP* pyr, const float* out_w, const float* out_b, const float* t, int score_mode, int HW, int total,
-    const float2* x, const float2* y, const float2* noise, uint64_t seed, uint64_t offset, const float* coef,
-    float2* x_out, float2* xmean_out, float2* score_out) {
+    const float2* x, const float2* y, const float2* noise, uint64_t seed, uint64_t offset, const uint64_t* row_seed,
+    const float* coef, float2* x_out, float2* xmean_out, float2* score_out) {
   const int p = blockIdx.x * 256 + threadIdx.x;
   if (p >= total) return;
   const int b = p / HW;
@@ -736,31 +747,34 @@ __global__ __launch_bounds__(256) void score_update_kernel(
   xm.x = cf[0] * xv.x + cf[1] * yv.x + cf[2] * sc.x;
   xm.y = cf[0] * xv.y + cf[1] * yv.y + cf[2] * sc.y;
   if (xmean_out) xmean_out[p] = xm;
-  float2 z = noise ? noise[p] : cnormal(seed, offset + (uint64_t)p);
+  float2 z = noise ? noise[p] : draw_normal(row_seed, seed, offset, p, b, HW);
   x_out[p] = make_float2(xm.x + cf[3] * z.x, xm.y + cf[3] * z.y);
 }
 
 // x = a x + by y + s z (prior sampling, sdes.py:225-232 / 298-304)
 __global__ __launch_bounds__(256) void axpby_noise_kernel(const float2* x, const float2* y, const float2* noise,
-                                                          uint64_t seed, uint64_t offset, const float* coef,
-                                                          int HW, int total, float2* out) {
+                                                          uint64_t seed, uint64_t offset,
+                                                          const uint64_t* row_seed, const float* coef, int HW,
+                                                          int total, float2* out) {
   const int p = blockIdx.x * 256 + threadIdx.x;
   if (p >= total) return;
-  const float* cf = coef + 4 * (p / HW);
+  const int b = p / HW;
+  const float* cf = coef + 4 * b;
   const float2 xv = x ? x[p] : make_float2(0.f, 0.f);
   const float2 yv = y ? y[p] : make_float2(0.f, 0.f);
-  const float2 z = noise ? noise[p] : cnormal(seed, offset + (uint64_t)p);
+  const float2 z = noise ? noise[p] : draw_normal(row_seed, seed, offset, p, b, HW);
   out[p] = make_float2(cf[0] * xv.x + cf[1] * yv.x + cf[3] * z.x, cf[0] * xv.y + cf[1] * yv.y + cf[3] * z.y);
 }
 
 // generic step for an arbitrary score tensor: x_mean = a x + by y + c score; x = x_mean + s z
 __global__ __launch_bounds__(256) void sde_update_kernel(const float2* x, const float2* y, const float2* score,
                                                          const float2* noise, uint64_t seed, uint64_t offset,
-                                                         const float* coef, int HW, int total, float2* x_out,
-                                                         float2* xmean_out) {
+                                                         const uint64_t* row_seed, const float* coef, int HW,
+                                                         int total, float2* x_out, float2* xmean_out) {
   const int p = blockIdx.x * 256 + threadIdx.x;
   if (p >= total) return;
-  const float* cf = coef + 4 * (p / HW);
+  const int b = p / HW;
+  const float* cf = coef + 4 * b;
   const float2 xv = x[p];
   const float2 yv = y ? y[p] : make_float2(0.f, 0.f);
   const float2 sc = score ? score[p] : make_float2(0.f, 0.f);
@@ -768,21 +782,34 @@ __global__ __launch_bounds__(256) void sde_update_kernel(const float2* x, const 
   xm.x = cf[0] * xv.x + cf[1] * yv.x + cf[2] * sc.x;
   xm.y = cf[0] * xv.y + cf[1] * yv.y + cf[2] * sc.y;
   if (xmean_out) xmean_out[p] = xm;
-  const float2 z = noise ? noise[p] : cnormal(seed, offset + (uint64_t)p);
+  const float2 z = noise ? noise[p] : draw_normal(row_seed, seed, offset, p, b, HW);
   x_out[p] = make_float2(xm.x + cf[3] * z.x, xm.y + cf[3] * z.y);
 }
 
 }  // namespace
 
-extern "C" int snrse_sde_update(const void* x, const void* y, const void* score, const void* noise, uint64_t seed,
-                                uint64_t offset, const float* coef, int B, int HW, void* x_out, void* xmean_out,
-                                hipStream_t s) {
+static int launch_sde_update(const void* x, const void* y, const void* score, const void* noise, uint64_t seed,
+                             uint64_t offset, const uint64_t* row_seed, const float* coef, int B, int HW,
+                             void* x_out, void* xmean_out, hipStream_t s) {
   const int total = B * HW;
   if (total <= 0 || !x || !coef || !x_out) return SNRSE_EINVAL;
   hipLaunchKernelGGL(sde_update_kernel, dim3((total + 255) / 256), dim3(256), 0, s, (const float2*)x,
-                     (const float2*)y, (const float2*)score, (const float2*)noise, seed, offset, coef, HW, total,
-                     (float2*)x_out, (float2*)xmean_out);
+                     (const float2*)y, (const float2*)score, (const float2*)noise, seed, offset, row_seed, coef, HW,
+                     total, (float2*)x_out, (float2*)xmean_out);
   return (int)hipGetLastError();
+}
+
+extern "C" int snrse_sde_update(const void* x, const void* y, const void* score, const void* noise, uint64_t seed,
+                                uint64_t offset, const float* coef, int B, int HW, void* x_out, void* xmean_out,
+                                hipStream_t s) {
+  return launch_sde_update(x, y, score, noise, seed, offset, nullptr, coef, B, HW, x_out, xmean_out, s);
+}
+
+extern "C" int snrse_sde_update_rs(const void* x, const void* y, const void* score, const void* noise,
+                                   const uint64_t* row_seed, uint64_t draw, const float* coef, int B, int HW,
+                                   void* x_out, void* xmean_out, hipStream_t s) {
+  if (!row_seed && !noise) return SNRSE_EINVAL;
+  return launch_sde_update(x, y, score, noise, 0, draw, row_seed, coef, B, HW, x_out, xmean_out, s);
 }
 
 extern "C" int snrse_temb_mlp(const float* t, const float* Wg, const float* W1, const float* b1,
@@ -887,10 +914,10 @@ extern "C" int snrse_input_pack(const void* x, const void* y, int B, int H, int 
   return (int)hipGetLastError();
 }
 
-extern "C" int snrse_score_update(const void* pyr, int pyr_f32, const float* out_w, const float* out_b,
-                                  const float* t, int score_mode, int B, int HW, const void* x, const void* y,
-                                  const void* noise, uint64_t seed, uint64_t offset, const float* coef,
-                                  void* x_out, void* xmean_out, void* score_out, hipStream_t s) {
+static int launch_score_update(const void* pyr, int pyr_f32, const float* out_w, const float* out_b, const float* t,
+                               int score_mode, int B, int HW, const void* x, const void* y, const void* noise,
+                               uint64_t seed, uint64_t offset, const uint64_t* row_seed, const float* coef,
+                               void* x_out, void* xmean_out, void* score_out, hipStream_t s) {
   const int total = B * HW;
   if (total <= 0 || !pyr || !x) return SNRSE_EINVAL;
   if (x_out && !coef) return SNRSE_EINVAL;
@@ -898,19 +925,47 @@ extern "C" int snrse_score_update(const void* pyr, int pyr_f32, const float* out
   if (pyr_f32)
     hipLaunchKernelGGL(score_update_kernel<float>, grid, dim3(256), 0, s, (const float*)pyr, out_w, out_b, t,
                        score_mode, HW, total, (const float2*)x, (const float2*)y, (const float2*)noise, seed,
-                       offset, coef, (float2*)x_out, (float2*)xmean_out, (float2*)score_out);
+                       offset, row_seed, coef, (float2*)x_out, (float2*)xmean_out, (float2*)score_out);
   else
     hipLaunchKernelGGL(score_update_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)pyr, out_w, out_b, t,
                        score_mode, HW, total, (const float2*)x, (const float2*)y, (const float2*)noise, seed,
-                       offset, coef, (float2*)x_out, (float2*)xmean_out, (float2*)score_out);
+                       offset, row_seed, coef, (float2*)x_out, (float2*)xmean_out, (float2*)score_out);
+  return (int)hipGetLastError();
+}
+
+extern "C" int snrse_score_update(const void* pyr, int pyr_f32, const float* out_w, const float* out_b,
+                                  const float* t, int score_mode, int B, int HW, const void* x, const void* y,
+                                  const void* noise, uint64_t seed, uint64_t offset, const float* coef,
+                                  void* x_out, void* xmean_out, void* score_out, hipStream_t s) {
+  return launch_score_update(pyr, pyr_f32, out_w, out_b, t, score_mode, B, HW, x, y, noise, seed, offset, nullptr,
+                             coef, x_out, xmean_out, score_out, s);
+}
+
+extern "C" int snrse_score_update_rs(const void* pyr, int pyr_f32, const float* out_w, const float* out_b,
+                                     const float* t, int score_mode, int B, int HW, const void* x, const void* y,
+                                     const void* noise, const uint64_t* row_seed, uint64_t draw, const float* coef,
+                                     void* x_out, void* xmean_out, void* score_out, hipStream_t s) {
+  if (x_out && !row_seed && !noise) return SNRSE_EINVAL;
+  return launch_score_update(pyr, pyr_f32, out_w, out_b, t, score_mode, B, HW, x, y, noise, 0, draw, row_seed, coef,
+                             x_out, xmean_out, score_out, s);
+}
+
+static int launch_axpby_noise(const void* x, const void* y, const void* noise, uint64_t seed, uint64_t offset,
+                              const uint64_t* row_seed, const float* coef, int B, int HW, void* out, hipStream_t s) {
+  const int total = B * HW;
+  if (total <= 0 || !coef || !out) return SNRSE_EINVAL;
+  hipLaunchKernelGGL(axpby_noise_kernel, dim3((total + 255) / 256), dim3(256), 0, s, (const float2*)x,
+                     (const float2*)y, (const float2*)noise, seed, offset, row_seed, coef, HW, total, (float2*)out);
   return (int)hipGetLastError();
 }
 
 extern "C" int snrse_axpby_noise(const void* x, const void* y, const void* noise, uint64_t seed, uint64_t offset,
                                  const float* coef, int B, int HW, void* out, hipStream_t s) {
-  const int total = B * HW;
-  if (total <= 0 || !coef || !out) return SNRSE_EINVAL;
-  hipLaunchKernelGGL(axpby_noise_kernel, dim3((total + 255) / 256), dim3(256), 0, s, (const float2*)x,
-                     (const float2*)y, (const float2*)noise, seed, offset, coef, HW, total, (float2*)out);
-  return (int)hipGetLastError();
+  return launch_axpby_noise(x, y, noise, seed, offset, nullptr, coef, B, HW, out, s);
+}
+
+extern "C" int snrse_axpby_noise_rs(const void* x, const void* y, const void* noise, const uint64_t* row_seed,
+                                    uint64_t draw, const float* coef, int B, int HW, void* out, hipStream_t s) {
+  if (!row_seed && !noise) return SNRSE_EINVAL;
+  return launch_axpby_noise(x, y, noise, 0, draw, row_seed, coef, B, HW, out, s);
 }

@@ -30,12 +30,21 @@ SNRSE_DEV void fill_twiddles(float* cs, float* sn) {
 }
 
 // mode: 0 = raw STFT, 1 = exponent transform (e = 0.5, factor 0.15)
-__global__ __launch_bounds__(256) void stft_kernel(const float* sig, int L, const float* in_div, float in_scale,
-                                                   int T, int Tpad, int mode, float2* out) {
+// Rows are `stride` samples apart.  lengths == nullptr: every row is L samples and T frames long.  Ragged
+// (lengths [B]): row b is valid on [0, L_b), reflects at its own L_b and has T_b = 1 + L_b / 128 frames; frames
+// [T_b, Tpad) are zero and no sample at or past L_b is read.  The host refuses L_b <= 255 and T_b > Tpad; the
+// clamps below only keep the addresses of a bad length inside the row.
+__global__ __launch_bounds__(256) void stft_kernel(const float* sig, int L, int stride, const int* lengths,
+                                                   const float* in_div, float in_scale, int T, int Tpad, int mode,
+                                                   float2* out) {
   __shared__ float cs[NFFT], sn[NFFT];
   __shared__ float xs[(FPB - 1) * HOP + NFFT];
   const int b = blockIdx.y;
   const int f0 = blockIdx.x * FPB;
+  if (lengths) {
+    L = min(max(lengths[b], 1), stride);
+    T = min(1 + L / HOP, Tpad);
+  }
   fill_twiddles(cs, sn);
   const int span = (FPB - 1) * HOP + NFFT;
   const float scale = in_div ? in_scale / in_div[b] : in_scale;
@@ -46,7 +55,7 @@ __global__ __launch_bounds__(256) void stft_kernel(const float* sig, int L, cons
     // frames >= T (zero padding up to Tpad) read past the reflect range; their output is
     // discarded, clamp the address so the load stays in bounds.
     s = s < 0 ? 0 : (s >= L ? L - 1 : s);
-    xs[j] = sig[(size_t)b * L + s] * scale;
+    xs[j] = sig[(size_t)b * stride + s] * scale;
   }
   __syncthreads();
   const int k = threadIdx.x;  // bin
@@ -147,11 +156,13 @@ __global__ __launch_bounds__(256) void istft_ola_kernel(const float* frames, int
   out[(size_t)b * L + i] = env > 1e-11f ? y / env * sc : 0.f;
 }
 
-// out[b] = max |sig[b, :]|  (norm_factor = y.abs().max(), model.py:726)
-__global__ __launch_bounds__(256) void absmax_kernel(const float* sig, int L, float* out) {
+// out[b] = max |sig[b, :]|  (norm_factor = y.abs().max(), model.py:726); ragged: over [0, L_b) of a `stride` row
+__global__ __launch_bounds__(256) void absmax_kernel(const float* sig, int L, int stride, const int* lengths,
+                                                     float* out) {
   const int b = blockIdx.x;
+  if (lengths) L = min(max(lengths[b], 0), stride);
   float m = 0.f;
-  for (int i = threadIdx.x; i < L; i += 256) m = fmaxf(m, fabsf(sig[(size_t)b * L + i]));
+  for (int i = threadIdx.x; i < L; i += 256) m = fmaxf(m, fabsf(sig[(size_t)b * stride + i]));
   m = wave_max(m);
   __shared__ float red[4];
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
@@ -190,7 +201,14 @@ extern "C" int snrse_spec_transform(const void* in, void* out, long long n, int 
 
 extern "C" int snrse_absmax(const float* sig, int B, int L, float* out, hipStream_t s) {
   if (B <= 0 || L <= 0 || !sig || !out) return SNRSE_EINVAL;
-  hipLaunchKernelGGL(absmax_kernel, dim3(B), dim3(256), 0, s, sig, L, out);
+  hipLaunchKernelGGL(absmax_kernel, dim3(B), dim3(256), 0, s, sig, L, L, (const int*)nullptr, out);
+  return (int)hipGetLastError();
+}
+
+extern "C" int snrse_absmax_ragged(const float* sig, const int* lengths, int B, int Lstride, float* out,
+                                   hipStream_t s) {
+  if (B <= 0 || Lstride <= 0 || !sig || !lengths || !out) return SNRSE_EINVAL;
+  hipLaunchKernelGGL(absmax_kernel, dim3(B), dim3(256), 0, s, sig, Lstride, Lstride, lengths, out);
   return (int)hipGetLastError();
 }
 
@@ -199,7 +217,20 @@ extern "C" int snrse_stft(const float* sig, int B, int L, const float* in_div, f
   const int T = 1 + L / HOP;
   if (B <= 0 || L <= NFFT / 2 || Tpad < T || (mode != 0 && mode != 1)) return SNRSE_EINVAL;
   dim3 grid((Tpad + FPB - 1) / FPB, B);
-  hipLaunchKernelGGL(stft_kernel, grid, dim3(256), 0, s, sig, L, in_div, in_scale, T, Tpad, mode, (float2*)out);
+  hipLaunchKernelGGL(stft_kernel, grid, dim3(256), 0, s, sig, L, L, (const int*)nullptr, in_div, in_scale, T, Tpad,
+                     mode, (float2*)out);
+  return (int)hipGetLastError();
+}
+
+// Ragged batch: sig [B, Lstride], lengths [B] int32 on the device.  The lengths cannot be read here without a
+// synchronisation: the caller checks 255 < L_b <= Lstride and 1 + L_b / 128 <= Tpad (snrse.ops.stft does).
+extern "C" int snrse_stft_ragged(const float* sig, const int* lengths, int B, int Lstride, const float* in_div,
+                                 float in_scale, int Tpad, int mode, void* out, hipStream_t s) {
+  if (B <= 0 || Lstride <= NFFT / 2 || Tpad <= 0 || !sig || !lengths || !out || (mode != 0 && mode != 1))
+    return SNRSE_EINVAL;
+  dim3 grid((Tpad + FPB - 1) / FPB, B);
+  hipLaunchKernelGGL(stft_kernel, grid, dim3(256), 0, s, sig, Lstride, Lstride, lengths, in_div, in_scale, 0, Tpad,
+                     mode, (float2*)out);
   return (int)hipGetLastError();
 }
 

@@ -150,7 +150,7 @@ class ScoreModel(nn.Module):
         def step(x, tv, coef, z, seed, off):
             pyr = net.pyramid(x, Yc, tv)
             xo, xm, _ = ops.score_update(pyr, net.W["out_w"], net.W["out_b"], tv, mode, x, Yc, coef=coef, noise=z,
-                                         seed=seed, offset=off)
+                                         offset=off, **_samp.row_seed_kw(seed))
             return xo, xm
 
         return step
@@ -329,6 +329,92 @@ class ScoreModel(nn.Module):
             rtf = (time.time() - start) / (len(x_hat) / 16000)
             return x_hat, nfe, rtf
         return x_hat
+
+    def _batch_route(self, sampler_type, corrector, kwargs):
+        """Which batched enhancer serves these settings: "pc", "snr", or None (the per-utterance loop)."""
+        if "noise_tape" in kwargs:
+            return None
+        if self.snr_conditioned == "true" and self.model_type == "sebridge_v3":
+            return "snr"
+        if (self.snr_conditioned == "false" and self.model_type == "bbed" and sampler_type == "pc"
+                and corrector in ("ald", "none")):
+            return "pc"
+        return None  # ODE sampler, the batch-mean `langevin` corrector, sebridge / sebridge_v2
+
+    @torch.no_grad()
+    def enhance_batch(self, ys, seeds=None, batch_size=32, max_frames=16384, sampler_type="pc",
+                      predictor="reverse_diffusion", corrector="ald", N=30, corrector_steps=1, snr=0.5, oracle=False,
+                      clean_rms=None, noise_rms=None, range_guard="auto", **kwargs):
+        """enhance() for a list of noisy utterances of different lengths (each [L], [1, L], numpy or tensor) ->
+        list of numpy [L_i] in input order.  Utterances whose spectrograms pad to the same frame count share a
+        ragged batch (snrse.batching.plan_batches: at most batch_size rows and max_frames frames per batch).
+
+        seeds: one noise seed per utterance; None draws one torch.randint(0, 2**62) each, in input order and before
+        any device work -- the draws a loop of enhance() calls makes, so under the same torch.manual_seed the
+        results are that loop's up to GEMM summation order, whatever batch_size is.  The PC sampler of a 'bbed'
+        model with the `ald` / `none` corrector runs on PCEnhancer and the SNR-conditioned 'sebridge_v3' one-step
+        model on SNRAlignedEnhancer (oracle=True takes clean_rms / noise_rms as sequences); every other setting
+        (ODE sampler, `langevin`, whose step size is a batch mean, sebridge / sebridge_v2, a noise_tape) loops
+        over enhance() and returns what it returns (seeds is not used there).  range_guard: enhance()'s
+        policies; "fallback" recomputes the flagged rows of a batch with the bf16 executor."""
+        from snrse import batching
+        from snrse.enhance import PCEnhancer, SNRAlignedEnhancer
+        n = len(ys)
+        route = self._batch_route(sampler_type, corrector, kwargs)
+        if route is None:
+            out = []
+            for i, y in enumerate(ys):
+                y = torch.as_tensor(np.asarray(y) if not torch.is_tensor(y) else y).reshape(1, -1)
+                out.append(self.enhance(y, y, sampler_type=sampler_type, predictor=predictor, corrector=corrector,
+                                        N=N, corrector_steps=corrector_steps, snr=snr, oracle=oracle,
+                                        clean_rms=clean_rms[i] if oracle else 1,
+                                        noise_rms=noise_rms[i] if oracle else 1, range_guard=range_guard, **kwargs))
+            return out
+        if seeds is None:
+            seeds = [_noise_seed() for _ in range(n)]
+        if len(seeds) != n:
+            raise ValueError(f"enhance_batch: {len(seeds)} seeds for {n} utterances")
+        if oracle and (clean_rms is None or noise_rms is None or len(clean_rms) != n or len(noise_rms) != n):
+            raise ValueError("enhance_batch(oracle=True) takes clean_rms and noise_rms, one value per utterance")
+        mode = self.data_module.hip_mode()
+        sigs = [torch.as_tensor(np.asarray(y) if not torch.is_tensor(y) else y).to(torch.float32).reshape(-1)
+                for y in ys]
+        lens = [int(s.numel()) for s in sigs]
+        plan = batching.plan_batches(lens, batch_size, max_frames)
+        dev = torch.device("cuda", torch.cuda.current_device())
+        out = [None] * n
+        with self._compute_format(self.RANGE_FALLBACK if self._range_fallback else self.dnn.compute_dtype):
+            net = self.dnn.hip(dev)
+            transform = "exponent" if mode == 1 else "none"
+            if route == "pc":
+                sde = self.sde.copy()
+                enh = PCEnhancer(net, sde.spec(), N=N, eps=self.t_eps, snr=snr, predictor=predictor,
+                                 corrector=corrector, corrector_steps=corrector_steps, score_mode=self._score_mode(),
+                                 transform=transform, guard=range_guard)
+            else:
+                snr_fn = None if oracle else (lambda raw: get_snr_model().estimate_from_spec(raw))
+                enh = SNRAlignedEnhancer(net, snr_fn=snr_fn, fixed_snr=float(self.fixed_snr),
+                                         sigma_max=float(self.sigma_max), transform=transform, guard=range_guard)
+            flagged = []
+            for rows in plan:
+                stride = max(lens[i] for i in rows)
+                buf = torch.zeros(len(rows), stride, dtype=torch.float32)
+                for r, i in enumerate(rows):
+                    buf[r, :lens[i]] = sigs[i]
+                yb = buf.to(dev)
+                ln = [lens[i] for i in rows]
+                rs = torch.tensor([seeds[i] for i in rows], dtype=torch.int64, device=dev)
+                if route == "pc":
+                    xb, _ = enh(yb, noise=_samp.NoiseSource(row_seeds=rs), lengths=ln)
+                else:
+                    est = [float(noise_rms[i]) / float(clean_rms[i]) for i in rows] if oracle else None
+                    xb, _ = enh(yb, est_snr=est, lengths=ln, row_seeds=rs)
+                flagged += [rows[r] for r in (enh.last_guard or {}).get("flagged", [])]
+                xb = xb.cpu().numpy()
+                for r, i in enumerate(rows):
+                    out[i] = xb[r, :lens[i]].copy()
+            self.last_guard = dict(enh.last_guard or {}, flagged=sorted(flagged))
+        return out
 
     RANGE_FALLBACK = "bf16"   # compute_dtype enhance() falls back to when fp16 overflows
     _range_fallback = False   # set by the first hit: this model then runs RANGE_FALLBACK

@@ -50,7 +50,7 @@ def get_pc_sampler(predictor_name, corrector_name, sde, score_fn, Y, Y_prior=Non
 
                 def step(x, tv, coef, z, sd_, off):
                     sc = score_fn(x[:, None], tv, Yc[:, None]).reshape(x.shape).to(torch.complex64).contiguous()
-                    return ops.sde_update(x, coef, y=Yc, score=sc, noise=z, seed=sd_, offset=off)
+                    return ops.sde_update(x, coef, y=Yc, score=sc, noise=z, offset=off, **_s.row_seed_kw(sd_))
 
             def score_tensor(x, tv):
                 return score_fn(x[:, None], tv, Yc[:, None]).reshape(x.shape).to(torch.complex64).contiguous()

@@ -38,6 +38,12 @@ SIGNATURES = {
     "snrse_score_update": [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _u64, _u64, _vp, _vp, _vp, _vp, _vp],
     "snrse_sde_update": [_vp, _vp, _vp, _vp, _u64, _u64, _vp, _i, _i, _vp, _vp, _vp],
     "snrse_axpby_noise": [_vp, _vp, _vp, _u64, _u64, _vp, _i, _i, _vp, _vp],
+    "snrse_score_update_rs": [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp],
+    "snrse_sde_update_rs": [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _i, _i, _vp, _vp, _vp],
+    "snrse_axpby_noise_rs": [_vp, _vp, _vp, _vp, _u64, _vp, _i, _i, _vp, _vp],
+    "snrse_stft_ragged": [_vp, _vp, _i, _i, _vp, _f, _i, _i, _vp, _vp],
+    "snrse_absmax_ragged": [_vp, _vp, _i, _i, _vp, _vp],
+    "snrse_energy_ratios_ragged": [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp],
     "snrse_stft": [_vp, _i, _i, _vp, _f, _i, _i, _vp, _vp],
     "snrse_absmax": [_vp, _i, _i, _vp, _vp],
     "snrse_range_stats": [_vp, _i, _ll, _i, _vp, _vp, _i, _vp],

@@ -25,8 +25,8 @@ def _chunks(buf: memoryview):
         off += 8 + size + (size & 1)
 
 
-def read_wav(path: str):
-    """-> (numpy float32 [frames, channels], sample_rate)."""
+def _layout(path: str):
+    """-> (memory map, fmt tuple, data offset, frame count) of a RIFF/WAVE file (chunk headers only are read)."""
     raw = np.memmap(path, dtype=np.uint8, mode="r")
     buf = memoryview(raw)
     if len(buf) < 12 or bytes(buf[0:4]) != b"RIFF" or bytes(buf[8:12]) != b"WAVE":
@@ -42,11 +42,22 @@ def read_wav(path: str):
             data = (off, min(size, len(buf) - off))
     if fmt is None or data is None:
         raise ValueError(f"{path}: missing fmt or data chunk")
-    tag, ch, sr, _, align, bits = fmt
+    _, ch, _, _, align, bits = fmt
     if ch < 1 or align != ch * ((bits + 7) // 8):
         raise ValueError(f"{path}: inconsistent fmt chunk")
-    off, size = data
-    n = size // align
+    return raw, fmt, data[0], data[1] // align
+
+
+def info(path: str):
+    """-> (frames, channels, sample_rate) from the headers alone: what load(path)'s tensor shape will be."""
+    _, fmt, _, n = _layout(path)
+    return n, fmt[1], fmt[2]
+
+
+def read_wav(path: str):
+    """-> (numpy float32 [frames, channels], sample_rate)."""
+    raw, fmt, off, n = _layout(path)
+    tag, ch, sr, _, align, bits = fmt
     b = raw[off:off + n * align]
     if tag == _PCM and bits == 16:
         x = b.view("<i2").astype(np.float32) / 32768.0

@@ -48,6 +48,26 @@ def transform_mode(transform):
     return TRANSFORM_MODES[transform]
 
 
+def ragged_lengths(lengths, y):
+    """(ops.Lengths, Tpad) of a ragged [B, Lstride] batch.  The rows must share Tpad = pad_frames(1 + L_b // 128):
+    then the network's shapes are those of each row's own run and the extra frames are the zero padding it would
+    have had alone (snrse.batching.plan_batches groups a file list this way)."""
+    B, L = y.shape
+    ln = ops.as_lengths(lengths, B, L, y.device)
+    tp = sorted({pad_frames(1 + int(v) // 128) for v in ln.host})
+    if len(tp) != 1:
+        raise ValueError(f"snrse: the rows of a ragged batch must share Tpad, got {tp} "
+                         "(snrse.batching.plan_batches groups utterances by it)")
+    return ln, tp[0]
+
+
+def crop_rows(x, ln):
+    """Zero x [B, Lstride] at and past each row's length.  The iSTFT's overlap-add depends on the frame count and
+    the sample index only, so computing to Lstride and cropping is exact on [0, L_b)."""
+    keep = torch.arange(x.shape[1], device=x.device)[None, :] < ln.dev[:, None]
+    return torch.where(keep, x, torch.zeros((), device=x.device, dtype=x.dtype))
+
+
 class PCEnhancer:
     """PC-sampler enhancement of a batch of noisy waveforms with an NCSNppHIP network.
 
@@ -85,7 +105,7 @@ class PCEnhancer:
         def step(x, tv, coef, z, seed, off):
             pyr = net.pyramid(x, Y, tv)
             xo, xm, _ = ops.score_update(pyr, net.W["out_w"], net.W["out_b"], tv, self.score_mode, x, Y,
-                                         coef=coef, noise=z, seed=seed, offset=off)
+                                         coef=coef, noise=z, offset=off, **sampler.row_seed_kw(seed))
             return xo, xm
 
         def score_tensor(x, tv):
@@ -155,14 +175,24 @@ class PCEnhancer:
             x.record_stream(cur)
         return torch.cat([x for x, _ in res]), res[0][1]
 
-    def __call__(self, y, noise=None):
-        """y [B, L] f32 device -> (x_hat [B, L] f32, nfe)."""
+    def __call__(self, y, noise=None, lengths=None):
+        """y [B, L] f32 device -> (x_hat [B, L] f32, nfe).  lengths: a ragged batch, row b valid on [0, L_b) of
+        the [B, Lstride] buffer (what lies past L_b is never read); the rows must share Tpad (ragged_lengths),
+        the result is zero past L_b.  A row's result equals its run alone up to GEMM summation order when
+        `noise` is row-seeded (sampler.NoiseSource(row_seeds=...)) and the corrector is not `langevin`."""
         B, L = y.shape
+        if lengths is not None:
+            ln, tpad = ragged_lengths(lengths, y)
+            nf = ops.absmax(y, lengths=ln)
+            Y = ops.stft(y, 1.0, tpad=tpad, mode=self.mode, in_div=nf, lengths=ln)
+            x, nfe = self.sample(Y, noise)
+            return crop_rows(ops.istft(x, L, mode=self.mode, out_scale=nf), ln), nfe
         nf = ops.absmax(y)  # norm_factor = max|y| (model.py:726)
         T = 1 + L // 128
         Y = ops.stft(y, 1.0, tpad=pad_frames(T), mode=self.mode, in_div=nf)
         x, nfe = self.sample(Y, noise)
         return ops.istft(x, L, mode=self.mode, out_scale=nf), nfe
+
 
 class SNRAlignedEnhancer:
     """One-step SNR-aligned enhancement of a batch (C4: model_type 'sebridge_v3',
@@ -184,20 +214,42 @@ class SNRAlignedEnhancer:
         self.mode = transform_mode(transform)
         self.fixed_snr, self.sigma_max = float(fixed_snr), float(sigma_max)
 
-    def __call__(self, y, est_snr=None, noise=None, seed=0):
+    def __call__(self, y, est_snr=None, noise=None, seed=0, lengths=None, row_seeds=None):
+        """lengths: a ragged batch (PCEnhancer.__call__), rows sharing Tpad; the SNR estimator, which reads a
+        spectrogram padded to 16 frames, runs once per group of rows with the same pad_frames(T_b, 16)
+        (batching.snr_groups) and the NCSN++ pass stays whole.  row_seeds (one per row): row b's prior noise is
+        Philox(row_seeds[b], e), what seed=row_seeds[b] draws for that row alone."""
         B, L = y.shape
-        nf = ops.absmax(y)
-        if est_snr is None:
+        ln = tpad = None
+        if lengths is not None:
+            ln, tpad = ragged_lengths(lengths, y)
+        nf = ops.absmax(y, lengths=ln)
+        if est_snr is None and ln is not None:
+            from .batching import snr_groups
+            est = torch.empty(B, dtype=torch.float64, device=y.device)
+            for T16, rows in snr_groups(ln.host):
+                idx = torch.tensor(rows, device=y.device)
+                sub = ops.Lengths(ln.host[rows], ln.dev[idx].contiguous())
+                raw = ops.stft(y[idx].contiguous(), 1.0, tpad=T16, mode=0, in_div=nf[idx].contiguous(), lengths=sub)
+                est[idx] = self.snr_fn(raw).reshape(len(rows)).double()
+            est_snr = est.cpu().numpy()
+        elif est_snr is None:
             T16 = pad_frames(1 + L // 128, 16)
             raw = ops.stft(y, 1.0, tpad=T16, mode=0, in_div=nf)  # no spec transform (model.py:715-719)
             est_snr = self.snr_fn(raw).reshape(B).double().cpu().numpy()
         t_hat = snap_t(est_snr, self.fixed_snr)
         div = nf * torch.from_numpy(normfac(t_hat, self.fixed_snr)).to(nf.device, torch.float32)
-        Y = ops.stft(y, 1.0, tpad=pad_frames(1 + L // 128), mode=self.mode, in_div=div)
+        if ln is not None:
+            Y = ops.stft(y, 1.0, tpad=tpad, mode=self.mode, in_div=div, lengths=ln)
+        else:
+            Y = ops.stft(y, 1.0, tpad=pad_frames(1 + L // 128), mode=self.mode, in_div=div)
         coef = torch.zeros(B, 4, dtype=torch.float32)
         coef[:, 1] = 1.0
         coef[:, 3] = torch.from_numpy(self.sigma_max * t_hat).float()
-        X_T = ops.axpby_noise(coef.to(Y.device), y=Y, noise=noise, seed=seed)
+        if row_seeds is not None:
+            X_T = ops.axpby_noise(coef.to(Y.device), y=Y, noise=noise, row_seeds=row_seeds)
+        else:
+            X_T = ops.axpby_noise(coef.to(Y.device), y=Y, noise=noise, seed=seed)
         tv = torch.from_numpy(t_hat).to(Y.device, torch.float32)
         sample = self.net.score(X_T, Y, tv, 1)
         # range guard (PCEnhancer): X_T does not depend on the network's format, so the flagged rows are one more
@@ -207,4 +259,5 @@ class SNRAlignedEnhancer:
         if _guard.report(self, rows, policy, self.fallback_dtype, self.net.dtype):
             fb = _guard.fallback_net(self.net, self.fallback_dtype)
             sample[rows] = fb.score(X_T[rows].contiguous(), Y[rows].contiguous(), tv[rows].contiguous(), 1)
-        return ops.istft(sample.contiguous(), L, mode=self.mode, out_scale=div.contiguous()), t_hat
+        out = ops.istft(sample.contiguous(), L, mode=self.mode, out_scale=div.contiguous())
+        return (out if ln is None else crop_rows(out, ln)), t_hat

@@ -12,7 +12,13 @@ Multi-GPU: files shard contiguously over ranks (snrse.dist.sh
 per-file metric rows meet on every rank with one all_gather (RCCL over xGMI on the GPU box,
 gloo in the CPU tests) and rank 0 writes the tables.
 
-    python -m snrse.evaluate --test_dir DIR --ckpt CKPT --destination_folder OUT [--N 30 ...]
+--batch_size B > 1 batches the rank's files: their lengths are read from the WAV headers, files whose
+spectrograms pad to the same frame count share a ragged batch (snrse.batching.plan_batches), each batch is one
+ScoreModel.enhance_batch call and one ragged snrse_energy_ratios launch.  Every file keeps the noise seed the
+per-file loop would draw for it, so the results do not depend on B beyond GEMM summation order.  The default,
+B = 1, is the per-file loop.
+
+    python -m snrse.evaluate --test_dir DIR --ckpt CKPT --destination_folder OUT [--N 30 --batch_size 32 ...]
 """
 from __future__ import annotations
 
@@ -64,8 +70,10 @@ def score_files(x_hat, x, y, sr=16000, pesq_fn=None):
 
 def evaluate(model, test_dir, target_dir, sampler_type="pc", predictor="reverse_diffusion", corrector="ald",
              corrector_steps=1, snr=0.5, N=30, reverse_starting_point=1.0, force_N=0, atol=1e-5, rtol=1e-5,
-             timestep_type="linear", correct_stepsize=False, oracle=False, rank=0, world=1, **enhance_kw):
-    """-> dict with 'filename' and METRICS lists (all files, every rank)."""
+             timestep_type="linear", correct_stepsize=False, oracle=False, rank=0, world=1, batch_size=1,
+             max_frames=16384, **enhance_kw):
+    """-> dict with 'filename' and METRICS lists (all files, every rank).  batch_size > 1: the rank's files run
+    as ragged batches of at most batch_size rows and max_frames spectrogram frames (_evaluate_batched)."""
     clean_dir, noisy_dir = join(test_dir, "clean"), join(test_dir, "noisy")
     os.makedirs(join(target_dir, "all"), exist_ok=True)
     if model.sde.__class__.__name__ == "OUVESDE":  # eval.py:105-108
@@ -84,6 +92,16 @@ def evaluate(model, test_dir, target_dir, sampler_type="pc", predictor="reverse_
     a, b = sdist.shard_range(len(files), rank, world)
     pesq_fn = _pesq_fn()
     rows = []
+    if batch_size > 1 and model._batch_route(sampler_type, corrector, enhance_kw) is None:
+        batch_size = 1  # no batched enhancer for these settings (ODE, sebridge / sebridge_v2): the per-file loop
+    if batch_size > 1:
+        rows = _evaluate_batched(model, files, a, b, clean_dir, target_dir, pesq_fn, batch_size, max_frames,
+                                 clean_rms, noise_rms,
+                                 dict(sampler_type=sampler_type, predictor=predictor, corrector=corrector,
+                                      corrector_steps=corrector_steps, N=N, snr=snr, atol=atol, rtol=rtol,
+                                      timestep_type=timestep_type, correct_stepsize=correct_stepsize, oracle=oracle,
+                                      **enhance_kw))
+        a = b  # the per-file loop below has nothing left
     for i in range(a, b):
         name = os.path.basename(files[i])
         x, sr = audio.load(join(clean_dir, name))
@@ -105,6 +123,54 @@ def evaluate(model, test_dir, target_dir, sampler_type="pc", predictor="reverse_
     if rank == 0:
         write_tables(data, target_dir)
     return data
+
+
+def score_batch(x_hat, x, y, dev=None):
+    """SI-SDR / SI-SIR / SI-SAR of a batch of files of different lengths (lists of 1-D numpy float32) in one
+    ragged snrse_energy_ratios launch: one [3, B, max L] upload, n = y - x formed on the device, file b scored
+    over its first L_b = min(len x_hat, len x, len y) samples as score_files does.  -> ([B, 3] numpy f64, [L_b])."""
+    dev = dev or torch.device("cuda", torch.cuda.current_device())
+    Ls = [min(len(h), len(c), len(n)) for h, c, n in zip(x_hat, x, y)]
+    sig = np.zeros((3, len(Ls), max(Ls)), np.float32)
+    for r, (h, c, n) in enumerate(zip(x_hat, x, y)):
+        sig[0, r, :Ls[r]], sig[1, r, :Ls[r]], sig[2, r, :Ls[r]] = h[:Ls[r]], c[:Ls[r]], n[:Ls[r]]
+    sd = torch.from_numpy(sig).to(dev)
+    return ops.energy_ratios(sd[0], sd[1], sd[2] - sd[1], lengths=Ls).cpu().numpy(), Ls
+
+
+def _evaluate_batched(model, files, a, b, clean_dir, target_dir, pesq_fn, batch_size, max_frames, clean_rms,
+                      noise_rms, kw):
+    """Metric rows of files [a, b), enhanced as ragged batches: lengths from the WAV headers, the plan, then per
+    batch one load, one enhance_batch call, the 16-bit files and one ragged energy_ratios launch with n = y - x
+    formed on the device; PESQ on the host, file by file.  The seeds are drawn first, one per file in file order:
+    the draws of the per-file loop under the same torch RNG state."""
+    from .batching import plan_batches
+    idx = list(range(a, b))
+    seeds = [int(torch.randint(0, 2 ** 62, (1,)).item()) for _ in idx]
+    lens = [audio.info(files[i])[0] for i in idx]
+    dev = torch.device("cuda", torch.cuda.current_device())
+    rows = [None] * len(idx)
+    oracle = kw["oracle"]
+    for batch in plan_batches(lens, batch_size, max_frames):
+        names = [os.path.basename(files[idx[k]]) for k in batch]
+        xs = [audio.load(join(clean_dir, nm)) for nm in names]
+        ys = [audio.load(files[idx[k]])[0] for k in batch]
+        x_hat = model.enhance_batch([y[0] for y in ys], seeds=[seeds[k] for k in batch], batch_size=len(batch),
+                                    max_frames=max_frames,
+                                    clean_rms=[clean_rms[idx[k]] for k in batch] if oracle else None,
+                                    noise_rms=[noise_rms[idx[k]] for k in batch] if oracle else None, **kw)
+        for nm, h in zip(names, x_hat):
+            audio.write_wav(join(target_dir, "all", nm), h, 16000, bits=16)
+        er, Ls = score_batch(x_hat, [x[0].numpy() for x, _ in xs], [y[0].numpy() for y in ys], dev)
+        for r, k in enumerate(batch):
+            p = float("nan")
+            if pesq_fn is not None:
+                try:
+                    p = float(pesq_fn(xs[r][1], xs[r][0][0, :Ls[r]].numpy(), x_hat[r][:Ls[r]], "wb"))
+                except Exception:  # as score_files: NaN for any PESQ failure (eval.py:147-150)
+                    p = float("nan")
+            rows[k] = [p, float(er[r, 0]), float(er[r, 1]), float(er[r, 2])]
+    return rows
 
 
 def sdist_backend_is_nccl():
@@ -143,6 +209,9 @@ def main(argv=None):
     ap.add_argument("--timestep_type", type=str, default="linear")
     ap.add_argument("--correct_stepsize", action="store_true")
     ap.add_argument("--oracle", action="store_true")
+    ap.add_argument("--batch_size", type=int, default=1,
+                    help="files per ragged batch (1 = the per-file loop; files of one batch share their padded "
+                         "frame count)")
     a = ap.parse_args(argv)
     rank, world, _ = sdist.init_from_env()
     from sgmse.model import ScoreModel
@@ -153,7 +222,7 @@ def main(argv=None):
              corrector=a.corrector, corrector_steps=a.corrector_steps, snr=a.snr, N=a.N,
              reverse_starting_point=a.reverse_starting_point, force_N=a.force_N, atol=a.atol, rtol=a.rtol,
              timestep_type=a.timestep_type, correct_stepsize=a.correct_stepsize, oracle=a.oracle, rank=rank,
-             world=world)
+             world=world, batch_size=a.batch_size)
 
 
 if __name__ == "__main__":

@@ -61,16 +61,18 @@ def runs(rows):
 
 
 def snapshot(noise: sampler.NoiseSource | None):
-    """A NoiseSource as the caller's is now (seed, tape, draw index), left untouched by the call it is taken for."""
+    """A NoiseSource as the caller's is now (seed, tape, row seeds, draw index), left untouched by the call it is
+    taken for."""
     noise = noise or sampler.NoiseSource()
-    snap = sampler.NoiseSource(noise.seed, noise.tape)
+    snap = sampler.NoiseSource(noise.seed, noise.tape, getattr(noise, "row_seeds", None))
     snap.i = noise.i
     return snap
 
 
 def run_noise(snap, rows_flagged, B):
     """[(a, b, LaneNoise)] per contiguous run of the flagged rows: the draws of rows [a, b) of the whole-batch run
-    that started at `snap`."""
+    that started at `snap` (a row-seeded snapshot hands each run the seeds of its rows).  The draws are those of
+    the whole batch as it was sampled: on a ragged batch each row's full Tpad-frame draws, which is what it drew."""
     return [(a, b, sampler.LaneNoise(snap, a, b, B)) for a, b in runs(rows_flagged)]
 
 

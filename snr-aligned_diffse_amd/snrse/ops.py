@@ -22,6 +22,7 @@ import os
 import threading
 import weakref
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -568,10 +569,21 @@ def input_pack(x, y, dtype):
     return col, pyr
 
 
+def _row_seeds(row_seeds, B, dev):
+    """Row seeds as the kernels read them: a contiguous int64 [B] tensor on `dev` (the bits of the uint64 keys)."""
+    if not torch.is_tensor(row_seeds):
+        row_seeds = torch.tensor([int(v) for v in row_seeds], dtype=torch.int64)
+    if row_seeds.dtype != torch.int64 or row_seeds.numel() != B:
+        raise ValueError(f"snrse: row_seeds must be {B} int64 values, one per batch row")
+    return row_seeds.to(dev).contiguous()
+
+
 def score_update(pyr, out_w, out_b, t, score_mode, x, y=None, coef=None, noise=None, seed=0, offset=0,
-                 want_score=False, x_out=None, xmean_out=None):
+                 want_score=False, x_out=None, xmean_out=None, row_seeds=None):
     """Output head + score + optional SDE step.  Returns (x_out, x_mean, score).  pyr: float32, or bfloat16 (the
-    library reads any other 16-bit pattern as bf16, so a float16 pyramid is refused here)."""
+    library reads any other 16-bit pattern as bf16, so a float16 pyramid is refused here).  row_seeds (int64 [B],
+    device): row b draws Philox(row_seeds[b], offset * HW + e) with `offset` the draw index, instead of the
+    batch-keyed Philox(seed, offset + index)."""
     if pyr.dtype not in (torch.float32, torch.bfloat16):
         raise TypeError(f"snrse: score_update takes a float32 or bfloat16 pyramid, got {pyr.dtype}")
     _dev(pyr, out_w, out_b, t, x, y, coef, noise)
@@ -583,6 +595,12 @@ def score_update(pyr, out_w, out_b, t, score_mode, x, y=None, coef=None, noise=N
         xmean_out = torch.empty_like(x) if xmean_out is None else xmean_out
     else:
         x_out = xmean_out = None
+    if row_seeds is not None:
+        rs = _row_seeds(row_seeds, B, x.device)
+        _lib.call("snrse_score_update_rs", pyr.data_ptr(), int(pyr.dtype == torch.float32), out_w.data_ptr(),
+                  out_b.data_ptr(), t.data_ptr(), int(score_mode), B, HW, x.data_ptr(), _ptr(y), _ptr(noise),
+                  rs.data_ptr(), int(offset), _ptr(coef), _ptr(x_out), _ptr(xmean_out), _ptr(score), _stream())
+        return x_out, xmean_out, score
     _lib.call("snrse_score_update", pyr.data_ptr(), int(pyr.dtype == torch.float32), out_w.data_ptr(),
               out_b.data_ptr(), t.data_ptr(), int(score_mode), B, HW, x.data_ptr(), _ptr(y), _ptr(noise),
               int(seed) & (2**64 - 1), int(offset), _ptr(coef), _ptr(x_out), _ptr(xmean_out), _ptr(score),
@@ -590,31 +608,71 @@ def score_update(pyr, out_w, out_b, t, score_mode, x, y=None, coef=None, noise=N
     return x_out, xmean_out, score
 
 
-def sde_update(x, coef, y=None, score=None, noise=None, seed=0, offset=0, x_out=None, xmean_out=None):
+def sde_update(x, coef, y=None, score=None, noise=None, seed=0, offset=0, x_out=None, xmean_out=None,
+               row_seeds=None):
     _dev(x, coef, y, score, noise)
     B = x.shape[0]
     HW = x.shape[-2] * x.shape[-1]
     x_out = torch.empty_like(x) if x_out is None else x_out
     xmean_out = torch.empty_like(x) if xmean_out is None else xmean_out
+    if row_seeds is not None:  # row-seeded draws (score_update): offset is the draw index
+        rs = _row_seeds(row_seeds, B, x.device)
+        _lib.call("snrse_sde_update_rs", x.data_ptr(), _ptr(y), _ptr(score), _ptr(noise), rs.data_ptr(), int(offset),
+                  coef.data_ptr(), B, HW, x_out.data_ptr(), xmean_out.data_ptr(), _stream())
+        return x_out, xmean_out
     _lib.call("snrse_sde_update", x.data_ptr(), _ptr(y), _ptr(score), _ptr(noise), int(seed) & (2**64 - 1),
               int(offset), coef.data_ptr(), B, HW, x_out.data_ptr(), xmean_out.data_ptr(), _stream())
     return x_out, xmean_out
 
 
-def axpby_noise(coef, x=None, y=None, noise=None, seed=0, offset=0, like=None):
+def axpby_noise(coef, x=None, y=None, noise=None, seed=0, offset=0, like=None, row_seeds=None):
     ref = x if x is not None else (y if y is not None else like)
     _dev(coef, x, y, noise)
     B = ref.shape[0]
     HW = ref.shape[-2] * ref.shape[-1]
     out = torch.empty_like(ref)
+    if row_seeds is not None:  # row-seeded draws (score_update): offset is the draw index
+        rs = _row_seeds(row_seeds, B, ref.device)
+        _lib.call("snrse_axpby_noise_rs", _ptr(x), _ptr(y), _ptr(noise), rs.data_ptr(), int(offset), coef.data_ptr(),
+                  B, HW, out.data_ptr(), _stream())
+        return out
     _lib.call("snrse_axpby_noise", _ptr(x), _ptr(y), _ptr(noise), int(seed) & (2**64 - 1), int(offset),
               coef.data_ptr(), B, HW, out.data_ptr(), _stream())
     return out
 
 
-def energy_ratios(s_hat, s, n=None):
+class Lengths:
+    """The valid lengths of a ragged [B, Lstride] batch: `.host` (numpy int64 [B], what the checks read) and
+    `.dev` (int32 [B] on the device, what the kernels read).  Built once per batch (as_lengths) so that the ops
+    of one enhancement neither upload nor read them back again."""
+
+    def __init__(self, host, dev):
+        self.host, self.dev = host, dev
+
+    def __len__(self):
+        return len(self.host)
+
+
+def as_lengths(lengths, B, Lstride, dev):
+    """lengths (Lengths, a sequence / numpy / CPU tensor, or an integer device tensor, which costs one read-back)
+    -> Lengths; every row must fit its buffer: 0 < L_b <= Lstride."""
+    if not isinstance(lengths, Lengths):
+        host = np.asarray(lengths.cpu() if torch.is_tensor(lengths) else lengths).astype(np.int64).reshape(-1)
+        lengths = Lengths(host, torch.from_numpy(host.astype(np.int32)).to(dev))
+    if len(lengths) != B:
+        raise ValueError(f"snrse: {len(lengths)} lengths for a batch of {B} rows")
+    bad = [int(i) for i in np.nonzero((lengths.host <= 0) | (lengths.host > Lstride))[0]]
+    if bad:
+        raise ValueError(f"snrse: lengths of rows {bad} are outside (0, {Lstride}], the row stride of the batch")
+    if lengths.dev.device != dev:
+        lengths = Lengths(lengths.host, lengths.dev.to(dev))
+    return lengths
+
+
+def energy_ratios(s_hat, s, n=None, lengths=None):
     """[B, L] f32 device waveforms -> [B, 3] f64 (SI-SDR, SI-SIR, SI-SAR) dB (utils.py:10-35);
-    without n only SI-SDR (column 0) is defined (sgmse/util/other.py:71-75)."""
+    without n only SI-SDR (column 0) is defined (sgmse/util/other.py:71-75).  lengths: ragged batch, row b's
+    dot products run over [0, L_b) and nothing past it is read."""
     B, L = s_hat.shape
     if s.shape != s_hat.shape or (n is not None and n.shape != s_hat.shape):
         raise ValueError("energy_ratios: s_hat, s, n must share one [B, L] shape")
@@ -622,15 +680,24 @@ def energy_ratios(s_hat, s, n=None):
     nn = None if n is None else n.to(torch.float32).contiguous()
     _dev(a[0], a[1], nn)
     out = torch.empty(B, 3, device=s_hat.device, dtype=torch.float64)
+    if lengths is not None:
+        ln = as_lengths(lengths, B, L, s_hat.device)
+        _lib.call("snrse_energy_ratios_ragged", a[0].data_ptr(), a[1].data_ptr(), _ptr(nn), ln.dev.data_ptr(), B, L,
+                  out.data_ptr(), _stream())
+        return out
     _lib.call("snrse_energy_ratios", a[0].data_ptr(), a[1].data_ptr(), _ptr(nn), B, L, out.data_ptr(), _stream())
     return out
 
 
-def absmax(sig):
-    """[B, L] f32 -> [B] max |sig| per row."""
+def absmax(sig, lengths=None):
+    """[B, L] f32 -> [B] max |sig| per row (ragged: over [0, L_b))."""
     _dev(sig)
     B, L = sig.shape
     out = torch.empty(B, device=sig.device, dtype=torch.float32)
+    if lengths is not None:
+        ln = as_lengths(lengths, B, L, sig.device)
+        _lib.call("snrse_absmax_ragged", sig.data_ptr(), ln.dev.data_ptr(), B, L, out.data_ptr(), _stream())
+        return out
     _lib.call("snrse_absmax", sig.data_ptr(), B, L, out.data_ptr(), _stream())
     return out
 
@@ -659,10 +726,24 @@ def range_stats(t, peak=None, nonfinite=None, accumulate=False):
     return peak, nonfinite
 
 
-def stft(sig, in_scale=1.0, tpad=None, mode=1, in_div=None):
-    """sig [B, L] f32 -> complex64 [B, 256, Tpad] of sig * in_scale / in_div[b]."""
+def stft(sig, in_scale=1.0, tpad=None, mode=1, in_div=None, lengths=None):
+    """sig [B, L] f32 -> complex64 [B, 256, Tpad] of sig * in_scale / in_div[b].  lengths: ragged batch, row b
+    reflects at its own L_b, has 1 + L_b // 128 frames and zeros after them; a row of 255 samples or fewer (too
+    short to reflect, as torch.stft refuses it) or with more frames than tpad fails as the library's EINVAL does."""
     _dev(sig, in_div)
     B, L = sig.shape
+    if lengths is not None:
+        if sig.dtype != torch.float32 or not sig.is_contiguous():
+            raise TypeError("snrse: a ragged stft takes a contiguous float32 [B, Lstride] buffer")
+        ln = as_lengths(lengths, B, L, sig.device)
+        tpad = 1 + int(ln.host.max()) // 128 if tpad is None else tpad
+        bad = [int(i) for i in np.nonzero((ln.host <= 255) | (1 + ln.host // 128 > tpad))[0]]
+        if bad:
+            _lib.check(1, f"snrse_stft_ragged (rows {bad}: 255 < L_b and 1 + L_b // 128 <= Tpad = {tpad} must hold)")
+        out = torch.empty(B, 256, tpad, device=sig.device, dtype=torch.complex64)
+        _lib.call("snrse_stft_ragged", sig.data_ptr(), ln.dev.data_ptr(), B, L, _ptr(in_div), float(in_scale), tpad,
+                  int(mode), out.data_ptr(), _stream())
+        return out
     T = 1 + L // 128
     tpad = T if tpad is None else tpad
     out = torch.empty(B, 256, tpad, device=sig.device, dtype=torch.complex64)

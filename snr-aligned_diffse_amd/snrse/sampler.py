@@ -125,26 +125,42 @@ def build_schedule(sde: SDESpec, N, eps, predictor, corrector, snr, corrector_st
 
 
 class NoiseSource:
-    """Draw i of the sampler: injected tensor (parity mode) or in-kernel Philox (seed, offset)."""
+    """Draw i of the sampler: injected tensor (parity mode) or in-kernel Philox.
 
-    def __init__(self, seed=0, tape=None):
+    Batch-keyed (the default): draw i of element p of the batch is Philox(seed, i * numel(batch) + p); next()
+    returns that counter offset.  Row-seeded (row_seeds, one per batch row, held as an int64 device tensor): draw i
+    of element e of row b is Philox(row_seeds[b], i * numel(row) + e) -- what a batch-keyed source with
+    seed = row_seeds[b] draws for that row run alone -- so an utterance's noise does not depend on the batch it
+    shares or on its row in it; next() then returns the draw index i, which the ops take as `offset` next to
+    row_seeds= (row_seed_kw)."""
+
+    def __init__(self, seed=0, tape=None, row_seeds=None):
         self.seed, self.tape, self.i = int(seed), tape, 0
+        if row_seeds is not None and not torch.is_tensor(row_seeds):
+            row_seeds = torch.tensor([int(v) for v in row_seeds], dtype=torch.int64)
+            if torch.cuda.is_available():
+                row_seeds = row_seeds.cuda()
+        self.row_seeds = row_seeds
 
     def next(self, numel):
         i = self.i
         self.i += 1
         if self.tape is not None:
             return self.tape(i), 0
+        if self.row_seeds is not None:
+            return None, i
         return None, i * numel
 
 
 class LaneNoise(NoiseSource):
     """The draws of batch rows [a, b) of a parent NoiseSource over the whole batch: the tape's row slice,
     or the parent's Philox counters of those elements (offset i * numel(batch) + a * numel(row)), so a
-    half-batch run on its own stream draws exactly the numbers the whole-batch run would."""
+    half-batch run on its own stream draws exactly the numbers the whole-batch run would.  Over a row-seeded
+    parent: the seeds of rows [a, b) and the parent's draw index."""
 
     def __init__(self, parent: NoiseSource, a, b, rows):
-        super().__init__(parent.seed, None)
+        rs = getattr(parent, "row_seeds", None)
+        super().__init__(parent.seed, None, None if rs is None else rs[a:b].contiguous())
         self.parent_tape, self.a, self.b, self.rows = parent.tape, a, b, rows
         self.i = parent.i  # continue where the parent's earlier draws left off
 
@@ -153,15 +169,24 @@ class LaneNoise(NoiseSource):
         self.i += 1
         if self.parent_tape is not None:
             return self.parent_tape(i)[self.a:self.b].contiguous(), 0
+        if self.row_seeds is not None:
+            return None, i
         row = numel // (self.b - self.a)
         return None, i * row * self.rows + self.a * row
+
+
+def row_seed_kw(seed):
+    """The `seed` a score_step receives as the ops' keywords: an int is the batch-keyed seed=, a tensor the
+    row_seeds= of a row-seeded NoiseSource."""
+    return {"row_seeds": seed} if torch.is_tensor(seed) else {"seed": seed}
 
 
 def pc_sample(score_step, Y, sde: SDESpec, N=30, eps=0.03, snr=0.5, predictor="reverse_diffusion",
               corrector="ald", corrector_steps=1, noise: NoiseSource | None = None, denoise=True,
               score_tensor=None, Y_prior=None, probability_flow=False):
     """Run the PC loop.  Y: complex64 [B, F, T] (device).
-    score_step(x, t_vec, coef_row, z, seed, offset) -> (x_new, x_mean) runs the network + fused step;
+    score_step(x, t_vec, coef_row, z, seed, offset) -> (x_new, x_mean) runs the network + fused step (over a
+    row-seeded NoiseSource `seed` is the int64 seed tensor and `offset` the draw index: see row_seed_kw);
     score_tensor(x, t_vec) -> complex score (only needed for the Langevin corrector).
     Returns (x_result, nfe)."""
     it = pc_sample_iter(score_step, Y, sde, N=N, eps=eps, snr=snr, predictor=predictor, corrector=corrector,
@@ -217,14 +242,16 @@ def pc_sample_iter(score_step, Y, sde: SDESpec, N=30, eps=0.03, snr=0.5, predict
     ttab = torch.tensor(np.repeat(np.asarray([t for _, t, _ in steps], dtype=np.float32)[:, None], B, axis=1),
                         device=dev)
     z, off = noise.next(numel)
-    x = ops.axpby_noise(ctab[-1], y=Y if Y_prior is None else Y_prior, noise=z, seed=noise.seed, offset=off)
+    rs = getattr(noise, "row_seeds", None)
+    key = noise.seed if rs is None else rs  # what score_step gets as `seed` (row_seed_kw turns it into keywords)
+    x = ops.axpby_noise(ctab[-1], y=Y if Y_prior is None else Y_prior, noise=z, offset=off, **row_seed_kw(key))
     x_mean = x
     ci = 0
     for si, (kind, t, cf) in enumerate(steps):
         tv = ttab[si]
         if kind in ("corr", "pred"):
             z, off = noise.next(numel)
-            x, x_mean = score_step(x, tv, ctab[ci], z, noise.seed, off)
+            x, x_mean = score_step(x, tv, ctab[ci], z, key, off)
             ci += 1
             yield
         elif kind == "langevin":
@@ -232,7 +259,7 @@ def pc_sample_iter(score_step, Y, sde: SDESpec, N=30, eps=0.03, snr=0.5, predict
             z, off = noise.next(numel)
             if z is None:  # Langevin needs the noise norm: materialise the draw
                 z = ops.axpby_noise(torch.tensor([[0.0, 0.0, 0.0, 1.0]] * B, device=dev, dtype=torch.float32),
-                                    like=Y, seed=noise.seed, offset=off)
+                                    like=Y, offset=off, **row_seed_kw(key))
             gn = torch.linalg.vector_norm(grad.reshape(B, -1), dim=-1).mean()
             nn_ = torch.linalg.vector_norm(z.reshape(B, -1), dim=-1).mean()
             e = (snr * nn_ / gn) ** 2 * 2
