@@ -249,11 +249,10 @@ SNRSE_DEV int epi_pix(int mb, int row, int seg_skip) {
   return TW == 64 ? mb + row : mb + row + (row / TW) * seg_skip;
 }
 
-// bias + temb of the lane's EPC channels of an epilogue_img call over channels nb .. nb + 63 of image b
+// bias + temb of the lane's EPC channels n .. n + EPC - 1 of image b
 template <typename TO, int EF>
-SNRSE_DEV void epi_add(const ConvParams& p, int nb, int lane, int b, float (&add)[16 / sizeof(TO)]) {
+SNRSE_DEV void epi_add_n(const ConvParams& p, int n, int b, float (&add)[16 / sizeof(TO)]) {
   constexpr int EPC = 16 / (int)sizeof(TO);
-  const int n = nb + (lane % (64 / EPC)) * EPC;
   const bool f_temb = EF < 0 ? p.temb != nullptr : (EF & EF_TEMB) != 0;
 #pragma unroll
   for (int k = 0; k < EPC; ++k) add[k] = 0.f;
@@ -268,6 +267,104 @@ SNRSE_DEV void epi_add(const ConvParams& p, int nb, int lane, int b, float (&add
     const float* tb = p.temb + (size_t)b * p.temb_stride + n;
 #pragma unroll
     for (int k = 0; k < EPC; ++k) add[k] += tb[k];
+  }
+}
+// ... of an epilogue_img call over channels nb .. nb + 63
+template <typename TO, int EF>
+SNRSE_DEV void epi_add(const ConvParams& p, int nb, int lane, int b, float (&add)[16 / sizeof(TO)]) {
+  constexpr int EPC = 16 / (int)sizeof(TO);
+  epi_add_n<TO, EF>(p, nb + (lane % (64 / EPC)) * EPC, b, add);
+}
+
+// Register epilogue of the v5 halo GEMM for 16-bit outputs: no LDS staging.  The kernel loads its weight rows
+// permuted (ring row 16 jj + lrow = cout n0 + 8 lrow + jj), so acc[h][i][j][e] is pixel 16 i + 4 lg + e of the wave's
+// 64, cout n0 + 8 lrow + 4 h + j: for one (i, e) a lane holds 8 adjacent couts = one 16-B output vector, the 16 lanes
+// of a row group the pixel's whole 256-B channel row of the tile, and one store instruction writes 4 pixels x 256 B.
+// bias / temb / Combine weights are per-lane constants, residual / Combine inputs one 16-B load per pixel, requested
+// LA pixels ahead.  The per-element fp32 operations and their order are epilogue_img's.  GN statistics: per lane over
+// its 16 pixels, summed over the four lg groups, left in `red` (the wave's 128 x 2 floats; the caller flushes).
+// The caller's out-of-range LDS-DMA pieces after the last phase are older than every load here, and vmcnt retires in
+// order: the wait for the constants below (all of this function's earlier loads when there is no look-ahead to leave
+// in flight) also waits for them.
+template <typename TO, int EF, int TW>
+SNRSE_DEV void epilogue_reg(const ConvParams& p, const f32x4 (&acc)[2][4][4], int mb, int n0, int lane, float* red,
+                            int b, int seg_skip) {
+  static_assert(sizeof(TO) == 2, "8 couts per 16-B vector");
+  const bool f_res = EF < 0 ? p.res != nullptr : (EF & EF_RES) != 0;
+  const bool f_comb = EF < 0 ? p.comb_src != nullptr : (EF & EF_COMB) != 0;
+  const bool f_stats = EF < 0 ? p.stats != nullptr : (EF & EF_STATS) != 0;
+  const bool f_nt = EF < 0 ? p.epi_nt != 0 : (EF & EF_NT) != 0;
+  const int lrow = lane & 15, lg = lane >> 4;
+  const int n = n0 + 8 * lrow;
+  float add[8];
+  epi_add_n<TO, EF>(p, n, b, add);
+  float cw[8][4], cb[8];
+  if (f_comb) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const f32x4 w = *(const f32x4*)(p.comb_w + (size_t)(n + k) * 4);
+      cw[k][0] = w[0]; cw[k][1] = w[1]; cw[k][2] = w[2]; cw[k][3] = w[3];
+      cb[k] = p.comb_b[n + k];
+    }
+  }
+  // look-ahead: the whole tile's residuals where the flags are compile-time and there is no Combine (64 VGPRs beside
+  // the 128 accumulators), else 4 pixels (Combine's weights take 40, the run-time form may have both inputs)
+  constexpr int LA = (EF >= 0 && !(EF & EF_COMB)) ? 16 : 4;
+  constexpr int NPRE = EF < 0 ? 0 : ((EF & EF_RES) ? LA : 0) + ((EF & EF_COMB) ? LA : 0);
+  u32x4 rpre[16];
+  f32x4 qpre[16];
+  // step t = (i, e): wave row 16 i + 4 lg + e
+  auto pix = [&](int t) { return (size_t)epi_pix<TW>(mb, 16 * (t >> 2) + 4 * lg + (t & 3), seg_skip); };
+  auto epi_issue = [&](int t) {
+    const size_t m = pix(t);
+    if (f_res) rpre[t] = *(const u32x4*)((const TO*)p.res + m * p.res_ld + n);
+    if (f_comb) qpre[t] = *(const f32x4*)(p.comb_src + m * 4);
+  };
+#pragma unroll
+  for (int t = 0; t < LA; ++t) epi_issue(t);
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NPRE) : "memory");
+  float s1[8], s2[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) { s1[k] = 0.f; s2[k] = 0.f; }
+#pragma unroll
+  for (int t = 0; t < 16; ++t) {
+    if (t + LA < 16) epi_issue(t + LA);
+    const int i = t >> 2, e = t & 3;
+    const size_t m = pix(t);
+    float v[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) v[k] = acc[k >> 2][i][k & 3][e] + add[k];
+    if (f_res) epi_residual<TO>(rpre[t], v);
+    if (p.out_scale != 1.f) {  // (uniform: Conv_0 and the other unscaled convs skip the multiply)
+#pragma unroll
+      for (int k = 0; k < 8; ++k) v[k] *= p.out_scale;
+    }
+    if (f_comb) {
+      const f32x4 q = qpre[t];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) v[k] += q[0] * cw[k][0] + q[1] * cw[k][1] + q[2] * cw[k][2] + q[3] * cw[k][3] + cb[k];
+    }
+    const u32x4 o = epi_pack<TO>(v);
+    if (f_nt)  // option "epi_nt": streaming (non-temporal) output stores
+      __builtin_nontemporal_store(o, (u32x4*)((TO*)p.out + m * p.out_ld + n));
+    else
+      *(u32x4*)((TO*)p.out + m * p.out_ld + n) = o;
+    if (f_stats) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) { s1[k] += v[k]; s2[k] = fmaf(v[k], v[k], s2[k]); }
+    }
+  }
+  if (f_stats) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      s1[k] = sum_lanes_strided<16>(s1[k]);
+      s2[k] = sum_lanes_strided<16>(s2[k]);
+    }
+    if (lg == 0) {
+#pragma unroll
+      for (int k = 0; k < 8; k += 2)
+        *(f32x4*)(red + (8 * lrow + k) * 2) = f32x4{s1[k], s2[k], s1[k + 1], s2[k + 1]};
+    }
   }
 }
 
@@ -1413,6 +1510,19 @@ __global__ __launch_bounds__(256) void conv_splitk_finalize(ConvParams p, int pp
 // no extra barrier.  (Round 4 ran the shortcut chunks after the main ones as one-tap chunks staged through registers
 // like a halo, whose HBM latency then had one tap of cover each: 3-6 % slower on every shortcut shape, +0.9 % on the
 // C2 line, profiles/r05b_h5_sc_*.)  SCD = the launch has a shortcut; without one the loop is the 3-phase chunk loop.
+//
+// Epilogue (round 9).  The MFMA's D layout gives a lane the couts of B column lane & 15 of each of its 8 B fragments.
+// With the rows in natural order (ring row r = cout n0 + r) those are the couts 16 jj + lrow, 32 B apart in memory, and
+// the tile had to pass through a 64 x 68 f32 LDS image per wave and half (128 ds_write_b32 + 32 ds_read_b128, behind a
+// workgroup barrier, because the image reused the ring and the halo).  For 16-bit outputs the weight rows are therefore
+// loaded permuted -- ring row 16 jj + lrow holds cout n0 + 8 lrow + jj; only the LDS-DMA source offsets differ, the
+// packed weights in HBM, the fragment reads and the MFMA order per accumulator do not -- so acc[h][i][j][e] is pixel
+// 16 i + 4 lg + e, cout n0 + 8 lrow + 4 h + j, and a lane stores 8 adjacent couts of a pixel straight from its
+// accumulators (epilogue_reg): no staging image, no barrier before the stores, and the statistics area has LDS of its
+// own.  The stored values are bit-identical to the staged epilogue's; the fp32 summation order of the GroupNorm
+// statistics differs.  (The other register-only form that was tried, D = [co][px] by swapping the MFMA operands, was
+// 3 % slower: each store scattered over 64 pixels.)  f32 outputs (two 16-B stores per pixel would be needed) keep the
+// staged epilogue_img and the natural row order.
 // T: the 16-bit input / weight format (bf16_t or f16_t), TO: the output type
 template <typename T, typename TO, int GNM, int EF, int TW, bool SCD>
 __global__ __launch_bounds__(256, 2) void conv_halo5_kernel(ConvParams p) {
@@ -1432,13 +1542,19 @@ __global__ __launch_bounds__(256, 2) void conv_halo5_kernel(ConvParams p) {
   // lanes of wave 0 before the chunk-end barrier and read by every thread's halo transform, so no
   // thread keeps them in registers across the MFMA phases
   float* const gnl = (float*)(smem + HALO_BYTES + 2 * SLOT + 1024);  // past the stamps build's area
+  // 16-bit outputs leave through the register epilogue (epilogue_reg); its statistics area has 4 KB of its own past
+  // the main-loop layout, since nothing separates a wave's epilogue from the other waves' last phase.  The f32
+  // output of the exact mode keeps the LDS-staged epilogue, which reuses the halo and the ring behind a barrier.
+  constexpr bool REGEPI = sizeof(TO) == 2;
+  constexpr int MAIN_BYTES = HALO_BYTES + 2 * SLOT + 1280;
+  constexpr int STAGE_BYTES = 4 * (64 * 68 * 4);
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
 #ifdef SNRSE_STAMPS
-  // past both the main-loop layout and the epilogue's staging + statistics area (which reuses the ring)
-  constexpr int kStampOff = (HALO_BYTES + 2 * SLOT + 1280) > (4 * (64 * 68 * 4) + 4 * 128 * 2 * 4)
-                                ? (HALO_BYTES + 2 * SLOT + 1280) : (4 * (64 * 68 * 4) + 4 * 128 * 2 * 4);
+  // past both the main-loop layout and the epilogue's statistics (and, f32 output, staging) area
+  constexpr int kStampOff = REGEPI ? MAIN_BYTES + 4096
+                                   : (MAIN_BYTES > STAGE_BYTES + 4096 ? MAIN_BYTES : STAGE_BYTES + 4096);
   unsigned long long* const lst = (unsigned long long*)(smem + kStampOff) + wid * 32;
 #endif
   SNRSE_STAMP(0);
@@ -1469,8 +1585,14 @@ __global__ __launch_bounds__(256, 2) void conv_halo5_kernel(ConvParams p) {
   // zeros land in the free ring slot), so every phase issues a fixed count (vm_after_dma).
   const int rl = lane >> 2, swz8 = ((lane & 3) ^ ((rl >> 1) & 3)) * 8;
   const __amdgpu_buffer_rsrc_t wrsrc = make_rsrc(p.wgt, p.wbytes);
-  const unsigned wlane = (unsigned)(((n0 + wid * 16 + rl) * K1 + swz8) * 2);
-  const unsigned wrow64 = (unsigned)(64 * K1 * 2), wtap = (unsigned)(Cin * 2);  // + 64 cout rows, + 1 tap
+  // REGEPI (16-bit outputs): the cout rows enter the ring permuted for the register epilogue -- ring row 16 jj + lrow
+  // (B fragment jj = wid + 4 (k & 1), lrow = rl) holds cout n0 + 8 lrow + jj, not n0 + 16 jj + lrow.  The LDS side of
+  // the DMA is fixed by the hardware (M0 + 16 lane), so only the source rows move: a piece still fetches 16 rows x
+  // 64 B from 16 different weight rows, and the B-fragment reads and the MFMA order do not change.
+  const int wr0 = REGEPI ? 8 * rl + wid : wid * 16 + rl;  // piece 0's cout row of this lane; the odd piece's is
+  constexpr int WODD = REGEPI ? 4 : 64;                   // WODD rows on
+  const unsigned wlane = (unsigned)(((n0 + wr0) * K1 + swz8) * 2);
+  const unsigned wrow64 = (unsigned)(WODD * K1 * 2), wtap = (unsigned)(Cin * 2);  // + the odd piece's rows, + 1 tap
   using lds_ptr = __attribute__((address_space(3))) void*;
   // piece k of a main phase with the phase offset soff (woff) and the per-lane offset vl (wlane, or out of range)
   auto dma_w = [&](auto k_, unsigned vl, unsigned soff, char* dst) {
@@ -1606,8 +1728,8 @@ __global__ __launch_bounds__(256, 2) void conv_halo5_kernel(ConvParams p) {
     // 1x1 weights' cout row; xpix: the pixel of this lane's tile row of piece 0 -- piece k is 64 k tile rows on)
     const __amdgpu_buffer_rsrc_t scrsrc = make_rsrc(p.sc_wgt, p.sc_wbytes);
     const __amdgpu_buffer_rsrc_t xrsrc0 = make_rsrc(p.sc_src, p.sc_bytes0), xrsrc1 = make_rsrc(p.sc_src1, p.sc_bytes1);
-    const unsigned sclane = (unsigned)(((n0 + wid * 16 + rl) * Csc_all + swz8) * 2);
-    const unsigned scrow64 = (unsigned)(64 * Csc_all * 2);
+    const unsigned sclane = (unsigned)(((n0 + wr0) * Csc_all + swz8) * 2);
+    const unsigned scrow64 = (unsigned)(WODD * Csc_all * 2);
     const int trow = wid * 16 + rl;
     const int xpix = (bb * p.H + h0 + trow / TW) * p.W + w0 + trow % TW;
     halo_load(0);
@@ -1825,24 +1947,40 @@ __global__ __launch_bounds__(256, 2) void conv_halo5_kernel(ConvParams p) {
   }
   }
   SNRSE_STAMP(28);
-  // both epilogue halves' bias + temb, requested before the drain below so that their round trip overlaps it
-  float add0[16 / sizeof(TO)], add1[16 / sizeof(TO)];
-  epi_add<TO, EF>(p, n0, lane, bb, add0);
-  epi_add<TO, EF>(p, n0 + 64, lane, bb, add1);
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // (the out-of-range DMA after the last phase too)
-  __builtin_amdgcn_s_barrier();  // LDS is reused as the epilogue staging area
-  float* const stage = (float*)(smem + wid * (64 * 68 * 4));
-  float* const red = (float*)(smem + 4 * (64 * 68 * 4));
+#ifdef SNRSE_H5_SKIP_EPI
+  // diagnostic build (never shipped): the tile without its epilogue, to read the epilogue's share of a launch
+  if (p.M > 0) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    return;
+  }
+#endif
   const int mrow = (bb * p.H + h0 + wid * RW) * p.W + w0;
-  // (f32 output, the exact mode: residuals two passes ahead -- acc[1] is still live here, 256 registers)
-  constexpr int ELA = sizeof(TO) == 2 ? 8 : 2;
-  epilogue_img<TO, 4, 128, true, EF, TW, ELA>(p, acc[0], mrow, n0, lane, stage, red, wid, bb, n0, p.W - TW, add0);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_wave_barrier();
-  SNRSE_STAMP(26);
-  epilogue_img<TO, 4, 128, true, EF, TW, ELA>(p, acc[1], mrow, n0 + 64, lane, stage, red, wid, bb, n0, p.W - TW, add1);
-  SNRSE_STAMP(27);
-  if (EF < 0 ? p.stats != nullptr : (EF & EF_STATS) != 0) block_stats_flush<4, 128>(p, red, bb, n0);
+  if constexpr (REGEPI) {
+    // no barrier and no LDS traffic but the statistics: a wave stores its 64 px x 128 couts from the accumulators
+    // while the other waves may still be in their last phase
+    float* const red = (float*)(smem + MAIN_BYTES);
+    epilogue_reg<TO, EF, TW>(p, acc, mrow, n0, lane, red + wid * 256, bb, p.W - TW);
+    SNRSE_STAMP(26);
+    SNRSE_STAMP(27);
+    if (EF < 0 ? p.stats != nullptr : (EF & EF_STATS) != 0) block_stats_flush<4, 128>(p, red, bb, n0);
+  } else {
+    // both epilogue halves' bias + temb, requested before the drain below so that their round trip overlaps it
+    float add0[16 / sizeof(TO)], add1[16 / sizeof(TO)];
+    epi_add<TO, EF>(p, n0, lane, bb, add0);
+    epi_add<TO, EF>(p, n0 + 64, lane, bb, add1);
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // (the out-of-range DMA after the last phase too)
+    __builtin_amdgcn_s_barrier();  // LDS is reused as the epilogue staging area
+    float* const stage = (float*)(smem + wid * (64 * 68 * 4));
+    float* const red = (float*)(smem + STAGE_BYTES);
+    // (the exact mode: residuals two passes ahead -- acc[1] is still live here, 256 registers)
+    epilogue_img<TO, 4, 128, true, EF, TW, 2>(p, acc[0], mrow, n0, lane, stage, red, wid, bb, n0, p.W - TW, add0);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+    SNRSE_STAMP(26);
+    epilogue_img<TO, 4, 128, true, EF, TW, 2>(p, acc[1], mrow, n0 + 64, lane, stage, red, wid, bb, n0, p.W - TW, add1);
+    SNRSE_STAMP(27);
+    if (EF < 0 ? p.stats != nullptr : (EF & EF_STATS) != 0) block_stats_flush<4, 128>(p, red, bb, n0);
+  }
 #ifdef SNRSE_STAMPS
   {
     unsigned long long st_[29];
@@ -1899,15 +2037,18 @@ inline int stream_output(const snrse_ctx& cx, long long bytes) {
 
 template <typename T, typename TO, int GNM, int EF, int TW, bool SCD>
 int launch_halo5_ef(ConvParams p, int grid, hipStream_t s) {
-  // halo + weight ring + (stamps build: 4 x 32 stamps) + the next chunk's GroupNorm affine (2 x 32 f32),
-  // and at least the epilogue's reuse of it: 4 waves' 64 x 68 f32 staging + the 4 x 128 x 2 f32 statistics
+  // halo + weight ring + (stamps build: 4 x 32 stamps) + the next chunk's GroupNorm affine (2 x 32 f32).  16-bit
+  // outputs (register epilogue): + the 4 x 128 x 2 f32 statistics.  f32 output: at least the staged epilogue's reuse
+  // of it, 4 waves' 64 x 68 f32 staging + the statistics.
   constexpr size_t main_lds = (256 / TW + 2) * (TW + 2) * 64 + 2 * 3 * 128 * 64 + 1024 + 256;
   constexpr size_t epi_lds = 4 * (64 * 68 * 4) + 4 * 128 * 2 * 4;
+  constexpr size_t used_lds = sizeof(TO) == 2 ? main_lds + 4 * 128 * 2 * 4 : (main_lds > epi_lds ? main_lds : epi_lds);
 #ifdef SNRSE_STAMPS
-  constexpr size_t lds = (main_lds > epi_lds ? main_lds : epi_lds) + 1024;  // + the 4 waves' stamps (kStampOff)
+  constexpr size_t lds = used_lds + 1024;  // + the 4 waves' stamps (kStampOff)
 #else
-  constexpr size_t lds = main_lds > epi_lds ? main_lds : epi_lds;
+  constexpr size_t lds = used_lds;
 #endif
+  static_assert(lds <= 80 * 1024, "two workgroups per CU");
   return launch_dyn_lds<conv_halo5_kernel<T, TO, GNM, EF, TW, SCD>>(dim3(grid), dim3(256), lds, s, p);
 }
 
