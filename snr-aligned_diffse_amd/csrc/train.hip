@@ -622,7 +622,9 @@ extern "C" int snrse_chan_sum(const float* x, int B, int HW, int C, float* out_b
 
 extern "C" int snrse_gn_moments(const double* st0, int C0, const double* st1, int C1, int B, int HW, int groups,
                                 float eps, float* mean, float* rstd, hipStream_t s) {
-  if (!st0 || (C1 && !st1) || B <= 0 || groups <= 0 || (C0 + C1) % groups) return SNRSE_EINVAL;
+  if (!st0 || !mean || !rstd || C0 <= 0 || C1 < 0 || (C1 && !st1) || B <= 0 || HW <= 0 || groups <= 0 ||
+      (C0 + C1) % groups)
+    return SNRSE_EINVAL;
   hipLaunchKernelGGL(gn_moments_kernel, dim3((B * groups + 255) / 256), dim3(256), 0, s, st0, C0, st1, C1, B, HW,
                      groups, eps, mean, rstd);
   return (int)hipGetLastError();
@@ -632,8 +634,10 @@ extern "C" int snrse_gn_backward(const float* x0, int C0, const float* x1, int C
                                  int groups, const float* gamma, const float* beta, const float* mean,
                                  const float* rstd, int act, float* R, float* dx0, float* dx1, float* dgamma,
                                  float* dbeta, hipStream_t s) {
+  if (!x0 || C0 <= 0 || C1 < 0 || (C1 && (!x1 || !dx1)) || !dy || !dx0 || !R || !gamma || !beta || !mean || !rstd ||
+      B <= 0 || HW <= 0 || groups <= 0 || (C0 + C1) % groups)
+    return SNRSE_EINVAL;
   const int C = C0 + C1;
-  if (!x0 || (C1 && (!x1 || !dx1)) || !dy || !dx0 || !R || B <= 0 || HW <= 0 || C % groups) return SNRSE_EINVAL;
   SNRSE_RET(hipMemsetAsync(R, 0, sizeof(float) * 2 * (size_t)B * C, s));
   const int ppb = 128;
   hipLaunchKernelGGL(gn_bwd_reduce_kernel, dim3((HW + ppb - 1) / ppb, B), dim3(256), 0, s, x0, C0, x1, C1, dy, HW,
