@@ -419,6 +419,19 @@ int snrse_ct_loss(const void* dnn1, const void* dnn0, const void* x1, const void
 int snrse_adam_ema(const void* tensors, const int* chunk_tensor, const long long* chunk_start, int nchunks,
                    float lr, float beta1, float beta2, float eps, float bias_corr1, float bias_corr2_sqrt,
                    float ema_decay, hipStream_t stream);
+/* The step with torch.nn.utils.clip_grad_norm_(norm_type = 2) and a gradient scale, without a host read-back:
+ * snrse_grad_sumsq writes partial[chunk] = sum g^2 (f64) for the chunks of a tensor table (a NULL g counts 0);
+ * snrse_grad_clip_coef folds npartials of them in a fixed order (bit-stable, no atomics) into
+ * out[0] = total_norm = accum_scale sqrt(sum) and out[1] = gscale = accum_scale min(1, max_norm /
+ * (total_norm + 1e-6)) (max_norm <= 0: no clipping, gscale = accum_scale); snrse_adam_ema_scaled is
+ * snrse_adam_ema with every gradient element multiplied by *gscale (device memory) first. */
+int snrse_grad_sumsq(const void* tensors, const int* chunk_tensor, const long long* chunk_start, int nchunks,
+                     double* partial, hipStream_t stream);
+int snrse_grad_clip_coef(const double* partial, int npartials, float max_norm, float accum_scale, float* out,
+                         hipStream_t stream);
+int snrse_adam_ema_scaled(const void* tensors, const int* chunk_tensor, const long long* chunk_start, int nchunks,
+                          float lr, float beta1, float beta2, float eps, float bias_corr1, float bias_corr2_sqrt,
+                          float ema_decay, const float* gscale, hipStream_t stream);
 
 #ifdef __cplusplus
 }

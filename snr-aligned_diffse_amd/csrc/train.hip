@@ -17,6 +17,9 @@
 //   snrse_ct_loss         sebridge_v3 preconditioning of both evaluations + mse / sqrt_mse loss and its
 //                         gradient w.r.t. both network outputs (model.py:378-390, 536-541)
 //   snrse_adam_ema        torch.optim.Adam step (+ torch_ema 0.3 shadow update) over many tensors, one launch
+//   snrse_grad_sumsq / snrse_grad_clip_coef / snrse_adam_ema_scaled
+//                         the same step with the global-norm clip of clip_grad_norm_ (Lightning's
+//                         gradient_clip_val) and a gradient scale, the factor computed and read on the device
 #include "common.h"
 
 #include <algorithm>
@@ -546,24 +549,86 @@ __global__ void ct_loss_kernel(const float2* dnn1, const float2* dnn0, const flo
 struct AdamTensor {
   float* p; const float* g; float* m; float* v; float* ema; long long n;
 };
-__global__ __launch_bounds__(256) void adam_ema_kernel(const AdamTensor* ts, const int* tix, const long long* start,
-                                                       float lr, float b1, float b2, float eps, float bc1, float bc2s,
-                                                       float ema_decay) {
+// SCALED: every gradient element is multiplied by gs (the clip / accumulation factor) before the moment updates
+template <bool SCALED>
+SNRSE_DEV void adam_ema_body(const AdamTensor* ts, const int* tix, const long long* start, float lr, float b1,
+                             float b2, float eps, float bc1, float bc2s, float ema_decay, float gs) {
   const AdamTensor T = ts[tix[blockIdx.x]];
   const long long s0 = start[blockIdx.x];
   const long long s1 = s0 + 2048 < T.n ? s0 + 2048 : T.n;
   const float step = lr / bc1;
   for (long long i = s0 + threadIdx.x; i < s1; i += 256) {
-    const float g = T.g ? T.g[i] : 0.f;
+    float g = T.g ? T.g[i] : 0.f;
+    if (SCALED) g *= gs;
+    // the two fused multiply-adds are spelled out (they are the contractions the compiler chose for the plain
+    // expressions of the unscaled kernel): left to itself it contracts the scaled variant's v the other way round,
+    // and a factor of exactly 1 would no longer give the unscaled kernel's bits
     float m = T.m[i];
-    m = m + (1.f - b1) * (g - m);
-    const float v = b2 * T.v[i] + (1.f - b2) * g * g;
+    m = fmaf(1.f - b1, g - m, m);
+    const float v = fmaf(g, (1.f - b2) * g, b2 * T.v[i]);
     T.m[i] = m;
     T.v[i] = v;
     const float denom = sqrtf(v) / bc2s + eps;
     const float p = T.p[i] - step * (m / denom);
     T.p[i] = p;
     if (T.ema) T.ema[i] = T.ema[i] - (1.f - ema_decay) * (T.ema[i] - p);
+  }
+}
+__global__ __launch_bounds__(256) void adam_ema_kernel(const AdamTensor* ts, const int* tix, const long long* start,
+                                                       float lr, float b1, float b2, float eps, float bc1, float bc2s,
+                                                       float ema_decay) {
+  adam_ema_body<false>(ts, tix, start, lr, b1, b2, eps, bc1, bc2s, ema_decay, 1.f);
+}
+__global__ __launch_bounds__(256) void adam_ema_scaled_kernel(const AdamTensor* ts, const int* tix,
+                                                              const long long* start, float lr, float b1, float b2,
+                                                              float eps, float bc1, float bc2s, float ema_decay,
+                                                              const float* gscale) {
+  adam_ema_body<true>(ts, tix, start, lr, b1, b2, eps, bc1, bc2s, ema_decay, *gscale);
+}
+
+// Global gradient norm of torch.nn.utils.clip_grad_norm_(norm_type=2) without a host read-back, over the same
+// tensor table and chunk list: partial[chunk] = sum g^2 in f64 (the square of an f32 is exact in f64; lanes by
+// shuffles, the 4 waves through LDS in wave order), then one block folds the partials in a fixed order -- no
+// float atomics anywhere, so the norm is bit-stable from run to run.
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const AdamTensor* ts, const int* tix, const long long* start,
+                                                         double* partial) {
+  __shared__ double wsum[4];
+  const AdamTensor T = ts[tix[blockIdx.x]];
+  const long long s0 = start[blockIdx.x];
+  const long long s1 = s0 + 2048 < T.n ? s0 + 2048 : T.n;
+  double acc = 0.0;
+  if (T.g)
+    for (long long i = s0 + threadIdx.x; i < s1; i += 256) {
+      const double g = (double)T.g[i];
+      acc = fma(g, g, acc);
+    }
+  acc = wave_sum_d(acc);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) partial[blockIdx.x] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+}
+
+// out[0] = total_norm = accum_scale sqrt(sum partial) (the norm of the gradients as the optimizer sees them),
+// out[1] = gscale = accum_scale min(1, max_norm / (total_norm + 1e-6)); max_norm <= 0: gscale = accum_scale.
+// A non-finite norm gives a NaN / zero factor as torch's clamp does.
+__global__ __launch_bounds__(256) void grad_clip_coef_kernel(const double* partial, int n, float max_norm,
+                                                             float accum_scale, float* out) {
+  __shared__ double wsum[4];
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256) acc += partial[i];
+  acc = wave_sum_d(acc);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const double ss = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+    const float tn = (float)((double)accum_scale * sqrt(ss));
+    float coef = 1.f;
+    if (max_norm > 0.f) {
+      const float c = max_norm / (tn + 1e-6f);
+      coef = c > 1.f ? 1.f : c;
+    }
+    out[0] = tn;
+    out[1] = accum_scale * coef;
   }
 }
 
@@ -714,6 +779,32 @@ extern "C" int snrse_adam_ema(const void* tensors, const int* chunk_tensor, cons
   if (!tensors || !chunk_tensor || !chunk_start || nchunks <= 0) return SNRSE_EINVAL;
   hipLaunchKernelGGL(adam_ema_kernel, dim3(nchunks), dim3(256), 0, s, (const AdamTensor*)tensors, chunk_tensor,
                      chunk_start, lr, beta1, beta2, eps, bias_corr1, bias_corr2_sqrt, ema_decay);
+  return (int)hipGetLastError();
+}
+
+extern "C" int snrse_adam_ema_scaled(const void* tensors, const int* chunk_tensor, const long long* chunk_start,
+                                     int nchunks, float lr, float beta1, float beta2, float eps, float bias_corr1,
+                                     float bias_corr2_sqrt, float ema_decay, const float* gscale, hipStream_t s) {
+  if (!tensors || !chunk_tensor || !chunk_start || nchunks <= 0 || !gscale) return SNRSE_EINVAL;
+  hipLaunchKernelGGL(adam_ema_scaled_kernel, dim3(nchunks), dim3(256), 0, s, (const AdamTensor*)tensors,
+                     chunk_tensor, chunk_start, lr, beta1, beta2, eps, bias_corr1, bias_corr2_sqrt, ema_decay,
+                     gscale);
+  return (int)hipGetLastError();
+}
+
+extern "C" int snrse_grad_sumsq(const void* tensors, const int* chunk_tensor, const long long* chunk_start,
+                                int nchunks, double* partial, hipStream_t s) {
+  if (!tensors || !chunk_tensor || !chunk_start || nchunks <= 0 || !partial) return SNRSE_EINVAL;
+  hipLaunchKernelGGL(grad_sumsq_kernel, dim3(nchunks), dim3(256), 0, s, (const AdamTensor*)tensors, chunk_tensor,
+                     chunk_start, partial);
+  return (int)hipGetLastError();
+}
+
+extern "C" int snrse_grad_clip_coef(const double* partial, int npartials, float max_norm, float accum_scale,
+                                    float* out, hipStream_t s) {
+  if (!partial || npartials <= 0 || !out) return SNRSE_EINVAL;
+  hipLaunchKernelGGL(grad_clip_coef_kernel, dim3(1), dim3(256), 0, s, partial, npartials, max_norm, accum_scale,
+                     out);
   return (int)hipGetLastError();
 }
 

@@ -5,7 +5,8 @@ Same constructor / attribute / method surface that eval.py and deep_eval.py use
 _stft, _istft, _forward_transform, _backward_transform, t_eps, sigma_max, fixed_snr,
 model_type, snr_conditioned) on top of the HIP runtime, plus the consistency-training step of the paper's model
 (_step / training_step / configure_optimizers / optimizer_step for sebridge_v3 with
-snr_conditioned 'true' / 'fixed', SURVEY.md §8(f) 2, snrse/train.py).  Validation logging and
+snr_conditioned 'true' / 'fixed', SURVEY.md §8(f) 2, snrse/train.py), validation_step and
+save_checkpoint for the training loop of snrse/fit.py.  The deep-inference validation block and
 the dead debug helpers (enhance_debug, prior_tests2, get_prior) are out of scope.
 
 Defined behaviour where the reference cannot run:
@@ -37,11 +38,16 @@ from . import sampling
 from .backbones import BackboneRegistry
 from .data_module import SpecsDataModule
 from .ema import EMAState, load_checkpoint
+from .ema import save_checkpoint as _save_checkpoint
 from .sdes import SDERegistry
 from .util.other import pad_spec, pad_spec_16, snr_dB  # noqa: F401  (re-exported like the reference)
 
 i_30 = np.arange(1, 30 + 1)
 t_30 = (0.001 ** (1 / 7) + (i_30 - 1) / (30 - 1) * (1 ** (1 / 7) - 0.001 ** (1 / 7))) ** 7
+
+# what ScoreModel._step and the training entry point (snrse.fit) say for the branches that are not built
+TRAIN_UNSUPPORTED = ("the HIP training step is built for model_type='sebridge_v3' with "
+                     "snr_conditioned 'true' / 'fixed' (the paper's consistency training)")
 
 SNR_CKPT = os.environ.get("SNRSE_SNR_CKPT", "./sgmse-bbed/sgmse/snr_estimator.ckpt")
 _snr_model = None
@@ -108,8 +114,17 @@ class ScoreModel(nn.Module):
 
     # ------------------------------------------------------------------ checkpoints / EMA
     @classmethod
-    def load_from_checkpoint(cls, checkpoint_path, map_location="cpu", weights_only=None, **overrides):
-        return load_checkpoint(cls, checkpoint_path, map_location, weights_only, overrides)
+    def load_from_checkpoint(cls, checkpoint_path, map_location="cpu", weights_only=None, optimizer=None,
+                             **overrides):
+        return load_checkpoint(cls, checkpoint_path, map_location, weights_only, overrides, optimizer=optimizer)
+
+    def save_checkpoint(self, path, optimizer=None, epoch=0, global_step=0, metrics=None):
+        """The Lightning checkpoint of this model (sgmse.ema.save_checkpoint): what load_from_checkpoint here
+        and the reference's read.  hyper_parameters are the constructor's arguments (model.py:93
+        save_hyperparameters), data_module_cls by name."""
+        hp = dict(self.hparams, lr=self.lr, ema_decay=self.ema_decay, loss_abs_exponent=self.loss_abs_exponent,
+                  num_eval_files=self.num_eval_files, loss_type=self.loss_type)
+        return _save_checkpoint(self, path, hp, optimizer, epoch, global_step, metrics)
 
     def train(self, mode=True, no_ema=False):
         res = super().train(mode)
@@ -176,8 +191,7 @@ class ScoreModel(nn.Module):
         loss tensor; loss.backward() runs the HIP backward kernels and fills the parameters' .grad."""
         from snrse import train as _train
         if self.model_type != "sebridge_v3" or self.snr_conditioned not in ("true", "fixed"):
-            raise NotImplementedError("the HIP training step is built for model_type='sebridge_v3' with "
-                                      "snr_conditioned 'true' / 'fixed' (the paper's consistency training)")
+            raise NotImplementedError(TRAIN_UNSUPPORTED)
         self.data_module._check()
         x, y = batch[0], batch[1]
         B = x.shape[0]
@@ -198,6 +212,13 @@ class ScoreModel(nn.Module):
 
     def training_step(self, batch, batch_idx):
         return self._step(batch, batch_idx, valid=False)
+
+    def validation_step(self, batch, batch_idx):
+        """model.py:402-404 without the Lightning logging: the loss of _step(valid=True), no autograd graph.
+        The enhancement metrics of model.py:408-429 come from sgmse.util.inference.evaluate_model, which the
+        training loop (snrse.fit) calls once per validation."""
+        with torch.no_grad():
+            return self._step(batch, batch_idx, valid=True)
 
     # ------------------------------------------------------------------ samplers
     def get_pc_sampler(self, predictor_name, corrector_name, y, Y_prior=None, N=None, minibatch=None,

@@ -2,7 +2,8 @@
 pytorch_lightning or torch_ema: forward(y) -> self.dnn(y) (SNRNet on the HIP runtime), checkpoint / EMA
 loading, and the training half -- _step / training_step / validation_step, configure_optimizers and
 optimizer_step -- on the HIP kernels of snrse.snr_train (forward + backward) and snrse.train.FusedAdam
-(Adam + EMA in one launch).  The Lightning Trainer / DDP / W&B loop of train_snr_est.py is out of scope."""
+(Adam + EMA in one launch); save_checkpoint writes what load_from_checkpoint reads.  The loop of
+train_snr_est.py is snrse.fit (--estimator); DDP and W&B are out of scope."""
 from __future__ import annotations
 
 import torch
@@ -10,6 +11,7 @@ import torch.nn as nn
 
 from .backbones.snrnet import SNRNet
 from .ema import EMAState, load_checkpoint
+from .ema import save_checkpoint as _save_checkpoint
 
 
 class SNRModel(nn.Module):
@@ -27,11 +29,18 @@ class SNRModel(nn.Module):
         self.dnn = SNRNet()
         self.lr, self.ema_decay, self.loss_type, self.num_eval_files = lr, ema_decay, loss_type, num_eval_files
         self.ema = EMAState(self)
+        self.hparams = dict(backbone=backbone, lr=lr, ema_decay=ema_decay, num_eval_files=num_eval_files,
+                            loss_type=loss_type, **kwargs)
         self.data_module = data_module_cls(**kwargs, gpu=kwargs.get("gpus", 0) > 0) if data_module_cls else None
 
     @classmethod
-    def load_from_checkpoint(cls, checkpoint_path, map_location="cpu", weights_only=None, **overrides):
-        return load_checkpoint(cls, checkpoint_path, map_location, weights_only, overrides)
+    def load_from_checkpoint(cls, checkpoint_path, map_location="cpu", weights_only=None, optimizer=None,
+                             **overrides):
+        return load_checkpoint(cls, checkpoint_path, map_location, weights_only, overrides, optimizer=optimizer)
+
+    def save_checkpoint(self, path, optimizer=None, epoch=0, global_step=0, metrics=None):
+        """The Lightning checkpoint of this model (sgmse.ema.save_checkpoint; snr_estimator.py:43, 62-63)."""
+        return _save_checkpoint(self, path, self.hparams, optimizer, epoch, global_step, metrics)
 
     def train(self, mode=True, no_ema=False):
         res = super().train(mode)

@@ -591,11 +591,20 @@ class FusedAdam(torch.optim.Optimizer):
     one launch per distinct per-tensor step count (torch's bias correction uses each tensor's own);
     `ema` (a sgmse.ema.EMAState) is updated in the same launch with torch_ema 0.3's rule,
     decay = min(decay, (1 + n) / (10 + n)), its shadows created from the parameters on first use; shadows of
-    parameters without a gradient move too (torch_ema updates every requires_grad shadow)."""
+    parameters without a gradient move too (torch_ema updates every requires_grad shadow).
 
-    def __init__(self, params, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, ema=None):
+    clip_grad_norm (torch.nn.utils.clip_grad_norm_'s max_norm, norm_type 2: Lightning's gradient_clip_val) and
+    step(grad_scale) (a factor on every gradient, as if the loss had been multiplied by it) run on the device:
+    snrse_grad_sumsq over every gradient, snrse_grad_clip_coef, then snrse_adam_ema_scaled, which reads the
+    factor from device memory -- three launches back to back, no host synchronisation.  The norm is taken once
+    over all tensors, whatever their step counts.  `last_grad_norm` is the norm of the (scaled, unclipped)
+    gradients as a device tensor; read it only to log.  With both at their defaults the plain launch runs."""
+
+    def __init__(self, params, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, ema=None, clip_grad_norm=None):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps))
         self.ema = ema
+        self.clip_grad_norm = clip_grad_norm
+        self.last_grad_norm = None
         self._chunk_cache = {}
 
     def _chunks(self, ps):
@@ -609,22 +618,29 @@ class FusedAdam(torch.optim.Optimizer):
         return (torch.tensor(tix, dtype=torch.int32, device=dev), torch.tensor(starts, dtype=torch.int64, device=dev))
 
     @torch.no_grad()
-    def step(self, closure=None):
+    def step(self, closure=None, grad_scale=1.0):
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        clip = float(self.clip_grad_norm or 0.0)
+        scaled_step = clip > 0.0 or float(grad_scale) != 1.0
         shadow_of = {}
         decay = 0.0
         if self.ema is not None:
             eps_ = self.ema._params()
             if self.ema.shadow_params is None:
                 self.ema.shadow_params = [p.detach().clone() for p in eps_]
+            elif any(s.device != p.device for s, p in zip(self.ema.shadow_params, eps_)):
+                # shadows loaded from a checkpoint live where it was mapped to: the launch needs them beside
+                # the parameters
+                self.ema.shadow_params = [s.to(p.device).contiguous() for s, p in zip(self.ema.shadow_params, eps_)]
             shadow_of = {id(p): s for p, s in zip(eps_, self.ema.shadow_params)}
             n_up = (0 if self.ema.num_updates is None else self.ema.num_updates) + 1
             self.ema.num_updates = n_up
             decay = min(self.ema.decay, (1 + n_up) / (10 + n_up))
         updated = set()
+        keep, launches = [], []
         for group in self.param_groups:
             ps = [p for p in group["params"] if p.grad is not None]
             if not ps:
@@ -643,7 +659,6 @@ class FusedAdam(torch.optim.Optimizer):
             by_step = {}
             for p in ps:
                 by_step.setdefault(int(self.state[p]["step"]), []).append(p)
-            keep = []
             for step, sub in by_step.items():
                 # chunk tables depend only on the element counts, in order (a recycled id() cannot serve a
                 # table of other sizes); a few entries at most, oldest evicted (gradient presence can vary)
@@ -664,13 +679,36 @@ class FusedAdam(torch.optim.Optimizer):
                     rec[i] = [p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(),
                               st["exp_avg_sq"].data_ptr(), 0 if sh is None else sh.data_ptr(), p.numel()]
                 table = torch.from_numpy(rec).to(sub[0].device)
-                keep.append(table)  # the launch reads it asynchronously
-                b1, b2 = group["betas"]
-                _call("snrse_adam_ema", table.data_ptr(), tix.data_ptr(), starts.data_ptr(),
-                      int(tix.numel()), float(group["lr"]), float(b1), float(b2), float(group["eps"]),
-                      float(1 - b1 ** step), float(math.sqrt(1 - b2 ** step)), float(decay))
-            self._keep = keep
+                keep += [table, tix, starts]  # the launches read them asynchronously
+                launches.append((group, step, table, tix, starts))
             updated.update(id(p) for p in ps)
+        gscale = self.last_grad_norm = None
+        if scaled_step and launches:
+            # one norm over every tensor of every launch: each writes its chunks' partial sums behind the
+            # previous one's, one fold turns them into (total_norm, gscale) in device memory
+            dev = launches[0][2].device
+            partial = torch.empty(sum(int(l[3].numel()) for l in launches), dtype=torch.float64, device=dev)
+            norm = torch.empty(2, dtype=torch.float32, device=dev)
+            off = 0
+            for _, _, table, tix, starts in launches:
+                _call("snrse_grad_sumsq", table.data_ptr(), tix.data_ptr(), starts.data_ptr(), int(tix.numel()),
+                      partial.data_ptr() + 8 * off)
+                off += int(tix.numel())
+            _call("snrse_grad_clip_coef", partial.data_ptr(), off, clip, float(grad_scale), norm.data_ptr())
+            keep += [partial, norm]
+            gscale = norm[1:]
+            self.last_grad_norm = norm[0]
+        for group, step, table, tix, starts in launches:
+            b1, b2 = group["betas"]
+            args = (table.data_ptr(), tix.data_ptr(), starts.data_ptr(), int(tix.numel()), float(group["lr"]),
+                    float(b1), float(b2), float(group["eps"]), float(1 - b1 ** step),
+                    float(math.sqrt(1 - b2 ** step)), float(decay))
+            if gscale is None:
+                _call("snrse_adam_ema", *args)
+            else:
+                _call("snrse_adam_ema_scaled", *args, gscale.data_ptr())
+        if launches:
+            self._keep = keep
         if self.ema is not None:
             # torch_ema 0.3 moves EVERY requires_grad shadow on every update, gradient or not:
             # s = decay s + (1 - decay) p for the parameters the fused launch did not touch
