@@ -432,6 +432,16 @@ int snrse_grad_clip_coef(const double* partial, int npartials, float max_norm, f
 int snrse_adam_ema_scaled(const void* tensors, const int* chunk_tensor, const long long* chunk_start, int nchunks,
                           float lr, float beta1, float beta2, float eps, float bias_corr1, float bias_corr2_sqrt,
                           float ema_decay, const float* gscale, hipStream_t stream);
+/* Multi-tensor gradient pack for the data-parallel all-reduce: over the same tensor table and chunk list,
+ * flat[flat_off[t] + i] = g_t[i] * scale for every element of every tensor t, one launch, one block per chunk (a
+ * NULL g writes zeros).  flat_off (device array, one entry per table row) holds each tensor's first element in
+ * flat and must be a multiple of 4 elements with flat itself 16-B aligned; elements of flat between the tensors
+ * are not written.  Stores are 16 B wide, loads too when the gradient's base is 16-B aligned; plain vector
+ * stores, no atomics.  hipErrorInvalidValue before any HIP call for nchunks < 0, a scale that is not finite or
+ * not > 0, or a NULL tensors / chunk_tensor / chunk_start / flat_off / flat with nchunks > 0; nchunks == 0 is a
+ * no-op that returns success. */
+int snrse_grad_pack(const void* tensors, const int* chunk_tensor, const long long* chunk_start, int nchunks,
+                    const long long* flat_off, float scale, float* flat, hipStream_t stream);
 
 #ifdef __cplusplus
 }

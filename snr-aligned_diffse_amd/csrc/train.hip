@@ -20,9 +20,12 @@
 //   snrse_grad_sumsq / snrse_grad_clip_coef / snrse_adam_ema_scaled
 //                         the same step with the global-norm clip of clip_grad_norm_ (Lightning's
 //                         gradient_clip_val) and a gradient scale, the factor computed and read on the device
+//   snrse_grad_pack       every gradient of the same tensor table times a scale into one flat buffer (the
+//                         data-parallel all-reduce's operand, snrse/dist.py GradReducer)
 #include "common.h"
 
 #include <algorithm>
+#include <cmath>
 
 namespace {
 
@@ -632,6 +635,40 @@ __global__ __launch_bounds__(256) void grad_clip_coef_kernel(const double* parti
   }
 }
 
+// Data-parallel gradient exchange: flat[flat_off[t] + i] = g_t[i] * scale over the optimizer's own tensor table
+// and chunk list, one block per 2048-element chunk.  A chunk starts at a multiple of 2048 elements and flat_off
+// is a multiple of 4, so the destination of a chunk is always 16-B aligned: stores are 16 B wide up to the last
+// n % 4 elements; loads are 16 B wide when the gradient's own base is 16-B aligned and scalar otherwise (a view
+// at an odd element offset).  A null g writes zeros.  One pass, no LDS, no atomics.
+__global__ __launch_bounds__(256) void grad_pack_kernel(const AdamTensor* ts, const int* tix, const long long* start,
+                                                        const long long* flat_off, float scale, float* flat) {
+  const int t = tix[blockIdx.x];
+  const AdamTensor T = ts[t];
+  const long long s0 = start[blockIdx.x];
+  const long long s1 = s0 + 2048 < T.n ? s0 + 2048 : T.n;
+  const int len = (int)(s1 - s0);
+  const int nvec = len >> 2;
+  float* dst = flat + flat_off[t] + s0;
+  const float* src = T.g ? T.g + s0 : nullptr;
+  float4* dst4 = reinterpret_cast<float4*>(dst);
+  if (!src) {
+    for (int i = threadIdx.x; i < nvec; i += 256) dst4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+  } else if ((reinterpret_cast<unsigned long long>(src) & 15ull) == 0) {
+    const float4* src4 = reinterpret_cast<const float4*>(src);
+    for (int i = threadIdx.x; i < nvec; i += 256) {
+      const float4 v = src4[i];
+      dst4[i] = make_float4(v.x * scale, v.y * scale, v.z * scale, v.w * scale);
+    }
+  } else {
+    for (int i = threadIdx.x; i < nvec; i += 256) {
+      const float* p = src + 4 * i;
+      dst4[i] = make_float4(p[0] * scale, p[1] * scale, p[2] * scale, p[3] * scale);
+    }
+  }
+  const int i = 4 * nvec + threadIdx.x;
+  if (i < len) dst[i] = src ? src[i] * scale : 0.f;
+}
+
 int grid_for(long long n) { return (int)std::min<long long>((n + 255) / 256, 65536); }
 
 }  // namespace
@@ -797,6 +834,16 @@ extern "C" int snrse_grad_sumsq(const void* tensors, const int* chunk_tensor, co
   if (!tensors || !chunk_tensor || !chunk_start || nchunks <= 0 || !partial) return SNRSE_EINVAL;
   hipLaunchKernelGGL(grad_sumsq_kernel, dim3(nchunks), dim3(256), 0, s, (const AdamTensor*)tensors, chunk_tensor,
                      chunk_start, partial);
+  return (int)hipGetLastError();
+}
+
+extern "C" int snrse_grad_pack(const void* tensors, const int* chunk_tensor, const long long* chunk_start, int nchunks,
+                               const long long* flat_off, float scale, float* flat, hipStream_t s) {
+  if (nchunks < 0 || !std::isfinite(scale) || !(scale > 0.f)) return SNRSE_EINVAL;
+  if (nchunks == 0) return 0;
+  if (!tensors || !chunk_tensor || !chunk_start || !flat_off || !flat) return SNRSE_EINVAL;
+  hipLaunchKernelGGL(grad_pack_kernel, dim3(nchunks), dim3(256), 0, s, (const AdamTensor*)tensors, chunk_tensor,
+                     chunk_start, flat_off, scale, flat);
   return (int)hipGetLastError();
 }
 

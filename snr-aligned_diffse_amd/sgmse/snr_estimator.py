@@ -3,7 +3,7 @@ pytorch_lightning or torch_ema: forward(y) -> self.dnn(y) (SNRNet on the HIP run
 loading, and the training half -- _step / training_step / validation_step, configure_optimizers and
 optimizer_step -- on the HIP kernels of snrse.snr_train (forward + backward) and snrse.train.FusedAdam
 (Adam + EMA in one launch); save_checkpoint writes what load_from_checkpoint reads.  The loop of
-train_snr_est.py is snrse.fit (--estimator); DDP and W&B are out of scope."""
+train_snr_est.py is snrse.fit (--estimator; --gpus N for its DDP); W&B is out of scope."""
 from __future__ import annotations
 
 import torch

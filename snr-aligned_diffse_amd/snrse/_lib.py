@@ -82,6 +82,7 @@ SIGNATURES = {
     "snrse_grad_sumsq": [_vp, _vp, _vp, _i, _vp, _vp],
     "snrse_grad_clip_coef": [_vp, _i, _f, _f, _vp, _vp],
     "snrse_adam_ema_scaled": [_vp, _vp, _vp, _i, _f, _f, _f, _f, _f, _f, _f, _vp, _vp],
+    "snrse_grad_pack": [_vp, _vp, _vp, _i, _vp, _f, _vp, _vp],
     # SNR-estimator training (csrc/snrnet_train.hip)
     "snrse_snr_perturb": [_vp, _vp, _vp, _i, _ll, _vp, _vp],
     "snrse_snrnet_train_fwd": [_vp, _i, _i] + [_vp] * 17 + [_vp, _vp, _vp],

@@ -617,6 +617,37 @@ class FusedAdam(torch.optim.Optimizer):
         dev = ps[0].device
         return (torch.tensor(tix, dtype=torch.int32, device=dev), torch.tensor(starts, dtype=torch.int64, device=dev))
 
+    def _chunk_list(self, sub):
+        """The cached chunk list of the tensors `sub`.  It depends only on the element counts, in order (a
+        recycled id() cannot serve a table of other sizes); a few entries at most, oldest evicted (gradient
+        presence can vary)."""
+        key = (str(sub[0].device),) + tuple(p.numel() for p in sub)
+        if key in self._chunk_cache:
+            self._chunk_cache[key] = self._chunk_cache.pop(key)  # most recently used last
+        else:
+            self._chunk_cache[key] = self._chunks(sub)
+            while len(self._chunk_cache) > 8:
+                self._chunk_cache.pop(next(iter(self._chunk_cache)))
+        return self._chunk_cache[key]
+
+    def grad_table(self, ps):
+        """(table, tix, starts, keep) for the gradients of `ps` as they are now: the step's own row layout and
+        cached chunk list, for a launch that reads gradients before the step (snrse.dist.GradReducer's pack).
+        Rows carry p, g and n; a parameter without a gradient gets a null g.  `keep` holds what the
+        asynchronous launch reads (contiguous copies of non-contiguous gradients, as in step()).  The table goes
+        up from pinned memory without blocking: a pageable copy would make the host wait for the backward still
+        in the queue, and everything the host does between here and the optimizer's launch would then show."""
+        tix, starts = self._chunk_list(ps)
+        rows, keep = [], []
+        for p in ps:
+            g = p.grad
+            if g is not None and not g.is_contiguous():
+                g = g.contiguous()
+            keep.append(g)
+            rows.append((p.data_ptr(), 0 if g is None else g.data_ptr(), 0, 0, 0, p.numel()))
+        table = torch.from_numpy(np.array(rows, dtype=np.int64)).pin_memory().to(ps[0].device, non_blocking=True)
+        return table, tix, starts, keep + [table]
+
     @torch.no_grad()
     def step(self, closure=None, grad_scale=1.0):
         loss = None
@@ -660,16 +691,7 @@ class FusedAdam(torch.optim.Optimizer):
             for p in ps:
                 by_step.setdefault(int(self.state[p]["step"]), []).append(p)
             for step, sub in by_step.items():
-                # chunk tables depend only on the element counts, in order (a recycled id() cannot serve a
-                # table of other sizes); a few entries at most, oldest evicted (gradient presence can vary)
-                key = (str(sub[0].device),) + tuple(p.numel() for p in sub)
-                if key in self._chunk_cache:
-                    self._chunk_cache[key] = self._chunk_cache.pop(key)  # most recently used last
-                else:
-                    self._chunk_cache[key] = self._chunks(sub)
-                    while len(self._chunk_cache) > 8:
-                        self._chunk_cache.pop(next(iter(self._chunk_cache)))
-                tix, starts = self._chunk_cache[key]
+                tix, starts = self._chunk_list(sub)
                 rec = np.zeros((len(sub), 6), dtype=np.int64)
                 for i, p in enumerate(sub):
                     st = self.state[p]
