@@ -274,7 +274,9 @@ int snrse_axpby_noise_rs(const void* x, const void* y, const void* noise, const 
 int snrse_energy_ratios(const float* s_hat, const float* s, const float* n, int B, int L, double* out,
                         hipStream_t stream);
 
-/* norm_factor = max |y| per utterance (model.py:726): out[b] = max_i |sig[b][i]|. */
+/* norm_factor = max |y| per utterance (model.py:726): out[b] = max_i |sig[b][i]|.  +-inf gives inf.  A NaN sample
+ * is skipped (the maximum is folded with fmaxf, which returns its other operand), where torch's abs().max()
+ * returns NaN: a row's result is the maximum of its non-NaN samples, 0 for a row of NaN only. */
 int snrse_absmax(const float* sig, int B, int L, float* out, hipStream_t stream);
 
 /* Ragged batches: utterances of different lengths in one [B][Lstride] f32 buffer with lengths [B] int32 on the

@@ -683,7 +683,9 @@ SNRSE_DEV u32x4 philox(u32x4 c, uint32_t k0, uint32_t k1) {
   }
   return c;
 }
-SNRSE_DEV float u01(uint32_t v) { return ((v >> 8) + 0.5f) * (1.0f / 16777216.0f); }  // (0,1)
+// [2^-25, 1]: (v >> 8) + 0.5f needs 25 bits from 2^23 on and rounds to even, so the top value gives exactly 1.0 --
+// harmless: logf(1) = 0 is a zero radius and the angle 2 pi is an angle like any other; 0 is never returned
+SNRSE_DEV float u01(uint32_t v) { return ((v >> 8) + 0.5f) * (1.0f / 16777216.0f); }
 
 SNRSE_DEV float2 cnormal(uint64_t seed, uint64_t ctr) {
   const u32x4 r = philox(u32x4{(uint32_t)ctr, (uint32_t)(ctr >> 32), 0x5eedu, 0u}, (uint32_t)seed,
