@@ -301,6 +301,33 @@ int snrse_stft_ragged(const float* sig, const int* lengths, int B, int Lstride, 
 int snrse_range_stats(const void* src, int B, long long per, int dtype, float* peak, int* nonfinite,
                       int accumulate, hipStream_t stream);
 
+/* ---- Stage kernels of the per-row adaptive RK45 (snrse/ode.py rk45_solve_rows; csrc/ode.hip).  Every row of a
+ * [B][n] float64 state (a complex128 state is n = 2 x elements doubles, pairs of reals) integrates with its own
+ * step h[b]; the controller stays on the host.  fp64 arithmetic without fma contraction: each product and sum
+ * rounds as numpy's and torch's do.  k / v: HOST arrays of ns <= 7 device pointers to stage tensors [B][n] of
+ * kdtype SNRSE_F32 (promoted in the load) or SNRSE_F64, c: HOST array of their ns coefficients (the caller drops
+ * zero coefficients; ns = 0 is a zero sum); both are copied into the launch.  Every tensor's base address must be
+ * 16-B aligned.  The results are the same bits on every launch (no floating-point atomics). */
+
+/* out[b][e] = y[b][e] + h[b] * (c_0 K_0[b][e] + c_1 K_1[b][e] + ...), summed in stage order; out32 (may be NULL):
+ * the float32 cast of out.  h [B] float64 on the device. */
+int snrse_rk45_combine(const double* y, const double* h, const void* const* k, const double* c, int ns, int kdtype,
+                       int B, long long n, double* out, float* out32, hipStream_t stream);
+
+/* out[b] = sqrt(mean_e |m[b] * sum_s c_s V_s[b][e]|^2 / (atol + rtol * max(|a[b][e]|, |b2[b][e]|))^2), |.| the
+ * complex modulus over pairs when cplx (n even) -- the error norm of a step (V = K, c = E, m = h, a = y,
+ * b2 = y_new) and the three norms of the initial step (b2 = a = y0, m NULL = 1).  Two passes: block partials
+ * partial [B][snrse_rk45_rownorm_blocks(B, n)] float64, then a fold in block order. */
+int snrse_rk45_rownorm(const void* const* v, const double* c, int ns, int vdtype, const double* m, const double* a,
+                       const double* b2, double rtol, double atol, int cplx, int B, long long n, double* partial,
+                       double* out, hipStream_t stream);
+int snrse_rk45_rownorm_blocks(int B, long long n);
+
+/* Rows with mask[b] != 0 (int32 [B], device): y[b] <- y_new[b] (ywords 32-bit words per row) and
+ * f[b] <- f_new[b] (fwords); every other row keeps its bits. */
+int snrse_rk45_accept(const int* mask, void* y, const void* y_new, long long ywords, void* f, const void* f_new,
+                      long long fwords, int B, hipStream_t stream);
+
 /* STFT (data_module.py:291-293 with spec_fwd 241-254 and pad_spec other.py:83-90):
  * sig [B][L] f32 -> out complex64 [B][256][Tpad], frames 1 + L/128 (the rest zero).
  * mode 0 raw, 1 exponent transform (|X|^0.5 e^{i angle X} * 0.15).  The signal is scaled by

@@ -352,7 +352,7 @@ class ScoreModel(nn.Module):
         return x_hat
 
     def _batch_route(self, sampler_type, corrector, kwargs):
-        """Which batched enhancer serves these settings: "pc", "snr", or None (the per-utterance loop)."""
+        """Which batched enhancer serves these settings: "pc", "ode", "snr", or None (the per-utterance loop)."""
         if "noise_tape" in kwargs:
             return None
         if self.snr_conditioned == "true" and self.model_type == "sebridge_v3":
@@ -360,7 +360,9 @@ class ScoreModel(nn.Module):
         if (self.snr_conditioned == "false" and self.model_type == "bbed" and sampler_type == "pc"
                 and corrector in ("ald", "none")):
             return "pc"
-        return None  # ODE sampler, the batch-mean `langevin` corrector, sebridge / sebridge_v2
+        if self.snr_conditioned == "false" and self.model_type == "bbed" and sampler_type == "ode":
+            return "ode"  # the corrector plays no part in the probability-flow ODE
+        return None  # the batch-mean `langevin` corrector, sebridge / sebridge_v2
 
     @torch.no_grad()
     def enhance_batch(self, ys, seeds=None, batch_size=32, max_frames=16384, sampler_type="pc",
@@ -375,11 +377,18 @@ class ScoreModel(nn.Module):
         results are that loop's up to GEMM summation order, whatever batch_size is.  The PC sampler of a 'bbed'
         model with the `ald` / `none` corrector runs on PCEnhancer and the SNR-conditioned 'sebridge_v3' one-step
         model on SNRAlignedEnhancer (oracle=True takes clean_rms / noise_rms as sequences); every other setting
-        (ODE sampler, `langevin`, whose step size is a batch mean, sebridge / sebridge_v2, a noise_tape) loops
+        (`langevin`, whose step size is a batch mean, sebridge / sebridge_v2, a noise_tape) loops
         over enhance() and returns what it returns (seeds is not used there).  range_guard: enhance()'s
-        policies; "fallback" recomputes the flagged rows of a batch with the bf16 executor."""
+        policies; "fallback" recomputes the flagged rows of a batch with the bf16 executor.
+
+        sampler_type="ode" on a 'bbed' model runs on ODEEnhancer: every row integrates the probability-flow ODE
+        with its own adaptive step sizes (kwargs rtol / atol, default 1e-5 as get_ode_sampler; N, timestep_type
+        and correct_stepsize are accepted and ignored).  Its prior is drawn from the per-utterance Philox seeds
+        like the PC route's, so the results do not depend on batch_size -- but they are a different noise
+        realisation from a loop over enhance(sampler_type="ode"), whose prior comes from torch's device
+        generator (sde.prior_sampling)."""
         from snrse import batching
-        from snrse.enhance import PCEnhancer, SNRAlignedEnhancer
+        from snrse.enhance import ODEEnhancer, PCEnhancer, SNRAlignedEnhancer
         n = len(ys)
         route = self._batch_route(sampler_type, corrector, kwargs)
         if route is None:
@@ -412,11 +421,16 @@ class ScoreModel(nn.Module):
                 enh = PCEnhancer(net, sde.spec(), N=N, eps=self.t_eps, snr=snr, predictor=predictor,
                                  corrector=corrector, corrector_steps=corrector_steps, score_mode=self._score_mode(),
                                  transform=transform, guard=range_guard)
+            elif route == "ode":
+                enh = ODEEnhancer(net, self.sde.copy().spec(), eps=self.t_eps, rtol=kwargs.get("rtol", 1e-5),
+                                  atol=kwargs.get("atol", 1e-5), score_mode=self._score_mode(), transform=transform,
+                                  guard=range_guard)
             else:
                 snr_fn = None if oracle else (lambda raw: get_snr_model().estimate_from_spec(raw))
                 enh = SNRAlignedEnhancer(net, snr_fn=snr_fn, fixed_snr=float(self.fixed_snr),
                                          sigma_max=float(self.sigma_max), transform=transform, guard=range_guard)
             flagged = []
+            ode_stats = self.last_ode_stats = []
             for rows in plan:
                 stride = max(lens[i] for i in rows)
                 buf = torch.zeros(len(rows), stride, dtype=torch.float32)
@@ -425,8 +439,10 @@ class ScoreModel(nn.Module):
                 yb = buf.to(dev)
                 ln = [lens[i] for i in rows]
                 rs = torch.tensor([seeds[i] for i in rows], dtype=torch.int64, device=dev)
-                if route == "pc":
-                    xb, _ = enh(yb, noise=_samp.NoiseSource(row_seeds=rs), lengths=ln)
+                if route in ("pc", "ode"):
+                    xb, nfe = enh(yb, noise=_samp.NoiseSource(row_seeds=rs), lengths=ln)
+                    if route == "ode":
+                        ode_stats.append(dict(enh.last_stats, files=list(rows), nfev=[int(v) for v in nfe]))
                 else:
                     est = [float(noise_rms[i]) / float(clean_rms[i]) for i in rows] if oracle else None
                     xb, _ = enh(yb, est_snr=est, lengths=ln, row_seeds=rs)
@@ -440,6 +456,7 @@ class ScoreModel(nn.Module):
     RANGE_FALLBACK = "bf16"   # compute_dtype enhance() falls back to when fp16 overflows
     _range_fallback = False   # set by the first hit: this model then runs RANGE_FALLBACK
     last_guard = None         # the latest enhance() call's guard record (snrse.guard.report)
+    last_ode_stats = None     # the latest enhance_batch() call's ODE batches: ODEEnhancer.last_stats + files, nfev
 
     @contextlib.contextmanager
     def _compute_format(self, fmt):

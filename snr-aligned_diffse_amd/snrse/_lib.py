@@ -18,7 +18,7 @@ from .build import LIB
 
 F32, BF16, F16, F64, F32X3 = 0, 1, 2, 3, 4
 
-_vp, _i, _f, _u64, _ll = C.c_void_p, C.c_int, C.c_float, C.c_uint64, C.c_longlong
+_vp, _i, _f, _u64, _ll, _d = C.c_void_p, C.c_int, C.c_float, C.c_uint64, C.c_longlong, C.c_double
 
 # name -> argtypes (all return int status except the housekeeping ones)
 SIGNATURES = {
@@ -87,10 +87,15 @@ SIGNATURES = {
     "snrse_snr_perturb": [_vp, _vp, _vp, _i, _ll, _vp, _vp],
     "snrse_snrnet_train_fwd": [_vp, _i, _i] + [_vp] * 17 + [_vp, _vp, _vp],
     "snrse_snrnet_backward": [_vp, _i, _i, _vp, _vp] + [_vp] * 8 + [_vp] + [_vp] * 17 + [_vp],
+    # per-row RK45 stage kernels (csrc/ode.hip)
+    "snrse_rk45_combine": [_vp, _vp, _vp, _vp, _i, _i, _i, _ll, _vp, _vp, _vp],
+    "snrse_rk45_rownorm": [_vp, _vp, _i, _i, _vp, _vp, _vp, _d, _d, _i, _i, _ll, _vp, _vp, _vp],
+    "snrse_rk45_accept": [_vp, _vp, _vp, _ll, _vp, _vp, _ll, _i, _vp],
 }
 HOUSEKEEPING = {"snrse_abi_version": ([], _i), "snrse_build_id": ([], C.c_char_p), "snrse_error_string": ([_i], C.c_char_p),
                 "snrse_device_name": ([C.c_char_p, _i], _i), "snrse_snrnet_workspace": ([_i, _i], C.c_size_t),
                 "snrse_snrnet_train_workspace": ([_i, _i], C.c_size_t),
+                "snrse_rk45_rownorm_blocks": ([_i, _ll], _i),
                 "snrse_ctx_create": ([], _vp), "snrse_ctx_destroy": ([_vp], None)}
 
 _lib = None

@@ -26,6 +26,8 @@ FLAGS = ["-O3", f"--offload-arch={ARCH}", "-std=c++17", "-fPIC", "-Wno-unused-re
 # 703 -> 686 us per launch, profiles/r02n_noslp_ab.json)
 FILE_FLAGS = {name: ["-fno-slp-vectorize"] for name in ("conv.hip", "conv_head.hip", "attn.hip", "score.hip",
                                                           "train.hip")}
+# The RK45 stage kernels restate numpy / torch float64 arithmetic: every product and sum rounds on its own, no fma
+FILE_FLAGS["ode.hip"] = ["-ffp-contract=off"]
 
 
 def _sources(csrc=CSRC):

@@ -15,8 +15,10 @@ per-utterance arithmetic as the B=1 ScoreModel.enhance (model.py:702-839):
     step, the network per utterance), iSTFT x max|y| per row;
   * 'sebridge_v3' + snr_conditioned 'true': snrse.enhance.SNRAlignedEnhancer (SNR from the estimator
     or, with --oracle, noise_rms / clean_rms; t_hat snapped per row);
-  * anything else (the adaptive ODE sampler, whose step sizes depend on the whole state; the
-    sebridge / sebridge_v2 one-step branches) runs the per-variant ScoreModel.enhance loop.
+  * model_type 'bbed' + ODE sampler: ScoreModel.enhance_batch's ODE route (snrse.enhance.ODEEnhancer), every
+    variant a row with its own adaptive step sizes and its own noise seed;
+  * anything else (the sebridge / sebridge_v2 one-step branches) runs the per-variant
+    ScoreModel.enhance loop.
 `si_sdr=True` adds si_sdr_<label> columns from snrse_energy_ratios (the reference keeps SI-SDR
 commented out in this script, deep_eval.py:146-148).
 
@@ -53,6 +55,8 @@ def snr_variants(x, y):
 def _batched_kind(model, sampler_type):
     if model.snr_conditioned == "false" and model.model_type == "bbed" and sampler_type == "pc":
         return "pc"
+    if model.snr_conditioned == "false" and model.model_type == "bbed" and sampler_type == "ode":
+        return "ode"
     if model.snr_conditioned == "true" and model.model_type == "sebridge_v3":
         return "snr_aligned"
     return None
@@ -66,6 +70,13 @@ def enhance_variants(model, ys, noise_rms, clean_rms=1.0, sampler_type="pc", pre
     the per-variant path then receives row k of each draw)."""
     V, L = ys.shape
     kind = _batched_kind(model, sampler_type) if batched else None
+    if kind == "ode" and noise_tape is not None:
+        kind = None  # an injected tape drives the per-variant path, as in ScoreModel._batch_route
+    if kind == "ode":
+        # the variants share a length: one batch, every row with its own adaptive steps and its own seed
+        seeds = [int(torch.randint(0, 2 ** 62, (1,)).item()) for _ in range(V)]
+        return np.stack(model.enhance_batch(list(ys), seeds=seeds, batch_size=V, max_frames=1 << 30,
+                                            sampler_type="ode", N=N, **kwargs))
     if kind is None:
         out = []
         for k in range(V):

@@ -7,6 +7,8 @@ Two branches, as the reference:
   * one-step SNR-aligned (model_type 'sebridge_v3', snr_conditioned 'true',
     model.py:713-740, 810-825): t_hat from the SNR (estimator or oracle rms) snapped to the
     t_30 grid, X_T = Y + sigma_max t_hat Z, one preconditioned NFE.
+The 'bbed' branch's other sampler, the probability-flow ODE (model.py:762-763, sampling/__init__.py:95-171), is
+ODEEnhancer: an adaptive RK45 in which every utterance of the batch keeps its own step sizes.
 Utterances are processed as a batch (the reference loops B=1); per-utterance scalars
 (norm factors, t_hat) stay per batch element.
 """
@@ -192,6 +194,113 @@ class PCEnhancer:
         Y = ops.stft(y, 1.0, tpad=pad_frames(T), mode=self.mode, in_div=nf)
         x, nfe = self.sample(Y, noise)
         return ops.istft(x, L, mode=self.mode, out_scale=nf), nfe
+
+
+class ODEEnhancer:
+    """Probability-flow ODE enhancement of a batch (the reference's get_ode_sampler, sampling/__init__.py:95-171,
+    which integrates one utterance at a time): prior x_T = Y + std(T) z, then dx/dt = kappa(t) (Y - x) - g(t)^2 / 2
+    score(x, t, Y) from T down to eps with the per-row adaptive RK45 (snrse.ode.rk45_solve_rows), then (denoise)
+    one noise-free reverse-diffusion update at eps with step size 0.03.
+
+    Every row has its own time, step size and accept / reject history, so a row's result is the solve it would have
+    had alone (up to GEMM summation order), however hard the rows it shares the batch with are; rows that reach
+    eps leave the batch and the network runs on the ones still integrating.  The drift is one net.pyramid plus one
+    fused ops.score_update with the per-row coefficients (-kappa, kappa, -g^2 / 2, 0), whose x_mean output is the
+    drift itself; kappa and g are taken at float32(t_b), the time the network is given (the per-utterance path
+    rounds its time vector the same way).  The RK45 stage combinations, error norms and per-row accepts are the
+    fp64 kernels of csrc/ode.hip; the controller is host float64 with one read-back (the B error norms) per attempt.
+
+    guard / fallback_dtype: PCEnhancer's policies.  A row whose error norm is not finite leaves the solve at once
+    (status -2); such rows and rows with a non-finite result are flagged, and "fallback" re-runs them through
+    net.fallback(fallback_dtype) from the same prior.  last_stats describes the latest sample(): `evals` calls of
+    the network, `row_evals` rows summed over them, per-row `attempts` and `status` (fallback re-runs excluded)."""
+
+    def __init__(self, net, sde: sampler.SDESpec, eps=0.03, rtol=1e-5, atol=1e-5, denoise=True, score_mode=0,
+                 transform="exponent", guard="auto", fallback_dtype=torch.bfloat16):
+        _guard.resolve(guard, net.dtype)
+        self.guard, self.fallback_dtype = guard, fallback_dtype
+        self.last_guard = self.last_stats = None
+        self.net, self.sde, self.eps, self.rtol, self.atol = net, sde, float(eps), float(rtol), float(atol)
+        self.denoise, self.score_mode = bool(denoise), score_mode
+        self.mode = transform_mode(transform)
+
+    def _fused(self, net, x32, Y, t64, coef_of):
+        """x_mean of one network evaluation + fused update at the per-row times t64 (host float64): the network
+        and the coefficients both see float32(t_b)."""
+        t32 = np.asarray(t64, dtype=np.float64).astype(np.float32)
+        coef = np.asarray([coef_of(float(t)) for t in t32], dtype=np.float32)
+        dev = Y.device
+        tv = torch.from_numpy(t32).pin_memory().to(dev, non_blocking=True)
+        cf = torch.from_numpy(coef).pin_memory().to(dev, non_blocking=True)
+        pyr = net.pyramid(x32, Y, tv)
+        return ops.score_update(pyr, net.W["out_w"], net.W["out_b"], tv, self.score_mode, x32, Y, coef=cf)[1]
+
+    def _pf_coef(self, t):
+        kap, g = self.sde.drift_coef(t), self.sde.g(t)
+        return (-kap, kap, -0.5 * g * g, 0.0)
+
+    def _denoise_coef(self, t, st=0.03):
+        kap, G = self.sde.drift_coef(t), self.sde.g(t) * math.sqrt(st)
+        return (1.0 + kap * st, -kap * st, G * G, 0.0)
+
+    def _solve(self, Y, noise, net):
+        from .ode import rk45_solve_rows
+        B = Y.shape[0]
+        prior = (0.0, 1.0, 0.0, self.sde.std(self.sde.T))  # build_schedule's prior coefficients
+        z, off = noise.next(Y.numel())
+        rs = getattr(noise, "row_seeds", None)
+        coef = torch.tensor([prior] * B, dtype=torch.float32, device=Y.device)
+        x0 = ops.axpby_noise(coef, y=Y, noise=z, offset=off, **sampler.row_seed_kw(noise.seed if rs is None else rs))
+        cache = {"rows": None, "Y": Y}
+
+        def drift(t, x, rows, x32):
+            if len(rows) != B:  # the live rows' Y, gathered once per change of the live set
+                key = tuple(int(r) for r in rows)
+                if cache["rows"] != key:
+                    cache["rows"], cache["Y"] = key, Y[rows.to(Y.device)].contiguous()
+            return self._fused(net, x32, cache["Y"] if len(rows) != B else Y, t.numpy(), self._pf_coef)
+
+        res = rk45_solve_rows(drift, self.sde.T, self.eps, x0, rtol=self.rtol, atol=self.atol, cast32=True)
+        x = res.y.to(torch.complex64)
+        if self.denoise:
+            x = self._fused(net, x, Y, [self.eps] * B, self._denoise_coef)
+        return x, res
+
+    def sample(self, Y, noise: sampler.NoiseSource | None = None):
+        """Y [B, F, T] complex64 -> (x [B, F, T] complex64, nfev numpy [B]): each row's evaluation count as
+        get_ode_sampler reports it for that row alone (2 + 6 x its attempts; the denoise step is not counted)."""
+        policy = _guard.resolve(self.guard, self.net.dtype)
+        noise = noise or sampler.NoiseSource()
+        snap = _guard.snapshot(noise) if policy == "fallback" else None
+        x, res = self._solve(Y, noise, self.net)
+        nfev = res.nfev.copy()
+        self.last_stats = {"evals": res.evals, "row_evals": res.row_evals, "status": [int(s) for s in res.status],
+                           "attempts": [len(h) + int(s == -2) for h, s in zip(res.history, res.status)]}
+        rows = []
+        if policy != "off":
+            rows = sorted(set(_guard.flagged_rows(x)) | {int(b) for b in np.nonzero(res.status == -2)[0]})
+        if _guard.report(self, rows, policy, self.fallback_dtype, self.net.dtype):
+            fb = _guard.fallback_net(self.net, self.fallback_dtype)
+            for a, b, lane in _guard.run_noise(snap, rows, Y.shape[0]):
+                x[a:b], r2 = self._solve(Y[a:b].contiguous(), lane, fb)
+                nfev[a:b] = r2.nfev
+        return x, nfev
+
+    def __call__(self, y, noise=None, lengths=None):
+        """y [B, L] f32 device -> (x_hat [B, L] f32, nfev numpy [B]).  lengths: a ragged batch under PCEnhancer's
+        rule (rows sharing Tpad, the result zero past L_b); with a row-seeded `noise` a row's result is its run
+        alone."""
+        B, L = y.shape
+        if lengths is not None:
+            ln, tpad = ragged_lengths(lengths, y)
+            nf = ops.absmax(y, lengths=ln)
+            Y = ops.stft(y, 1.0, tpad=tpad, mode=self.mode, in_div=nf, lengths=ln)
+            x, nfev = self.sample(Y, noise)
+            return crop_rows(ops.istft(x.contiguous(), L, mode=self.mode, out_scale=nf), ln), nfev
+        nf = ops.absmax(y)
+        Y = ops.stft(y, 1.0, tpad=pad_frames(1 + L // 128), mode=self.mode, in_div=nf)
+        x, nfev = self.sample(Y, noise)
+        return ops.istft(x.contiguous(), L, mode=self.mode, out_scale=nf), nfev
 
 
 class SNRAlignedEnhancer:

@@ -16,7 +16,9 @@ gloo in the CPU tests) and rank 0 writes the tables.
 spectrograms pad to the same frame count share a ragged batch (snrse.batching.plan_batches), each batch is one
 ScoreModel.enhance_batch call and one ragged snrse_energy_ratios launch.  Every file keeps the noise seed the
 per-file loop would draw for it, so the results do not depend on B beyond GEMM summation order.  The default,
-B = 1, is the per-file loop.
+B = 1, is the per-file loop.  With --sampler_type ode a batch integrates every file with its own adaptive RK45
+steps (snrse.enhance.ODEEnhancer); there B > 1 takes the prior from the per-file seeds, B = 1 from torch's device
+generator, so the two are different noise realisations.
 
     python -m snrse.evaluate --test_dir DIR --ckpt CKPT --destination_folder OUT [--N 30 --batch_size 32 ...]
 """
@@ -73,7 +75,12 @@ def evaluate(model, test_dir, target_dir, sampler_type="pc", predictor="reverse_
              timestep_type="linear", correct_stepsize=False, oracle=False, rank=0, world=1, batch_size=1,
              max_frames=16384, **enhance_kw):
     """-> dict with 'filename' and METRICS lists (all files, every rank).  batch_size > 1: the rank's files run
-    as ragged batches of at most batch_size rows and max_frames spectrogram frames (_evaluate_batched)."""
+    as ragged batches of at most batch_size rows and max_frames spectrogram frames (_evaluate_batched).
+
+    sampler_type="ode" with batch_size > 1 runs ScoreModel.enhance_batch's ODE route: every file integrates with
+    its own adaptive step sizes and draws its prior from its own Philox seed, so the results do not depend on
+    batch_size as long as it is > 1 -- but they are a different noise realisation from batch_size = 1, whose
+    per-file enhance() loop draws the prior from torch's device generator."""
     clean_dir, noisy_dir = join(test_dir, "clean"), join(test_dir, "noisy")
     os.makedirs(join(target_dir, "all"), exist_ok=True)
     if model.sde.__class__.__name__ == "OUVESDE":  # eval.py:105-108
@@ -93,7 +100,7 @@ def evaluate(model, test_dir, target_dir, sampler_type="pc", predictor="reverse_
     pesq_fn = _pesq_fn()
     rows = []
     if batch_size > 1 and model._batch_route(sampler_type, corrector, enhance_kw) is None:
-        batch_size = 1  # no batched enhancer for these settings (ODE, sebridge / sebridge_v2): the per-file loop
+        batch_size = 1  # no batched enhancer for these settings (langevin, sebridge / sebridge_v2): the per-file loop
     if batch_size > 1:
         rows = _evaluate_batched(model, files, a, b, clean_dir, target_dir, pesq_fn, batch_size, max_frames,
                                  clean_rms, noise_rms,

@@ -19,6 +19,9 @@ the host (step acceptance).  Restated from scipy 1.8.0's `RungeKutta` / `RK45`:
   nfev = 2 + 6 x attempts, as `solve_ivp(...).nfev` counts.
 
 Test infrastructure checks it against scipy itself (tests/test_ode.py).
+
+`rk45_solve_rows` is the same algorithm for a batch of independent ODEs, the controller's scalars kept per row
+(tests/test_ode_rows.py against scipy row by row; its per-element work runs on the kernels of csrc/ode.hip).
 """
 from __future__ import annotations
 
@@ -166,3 +169,266 @@ def rk45_solve(fun: Callable[[float, torch.Tensor], torch.Tensor], t0: float, t_
             status = 0
     return OdeResult(y=y, t=t, nfev=nfev, status=status, message=message or "The solver successfully reached "
                      "the end of the integration interval.", n_accepted=n_acc, n_rejected=n_rej)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Per-row solver: a batch of independent ODEs, every row with its own time, step size and accept / reject history
+
+
+@dataclass
+class OdeRowsResult:
+    y: torch.Tensor          # [B, ...] final states (the solver's dtype); all NaN for a row with status -2
+    t: np.ndarray            # [B] float64 time each row stopped at
+    nfev: np.ndarray         # [B] evaluations of each row (2 + 6 x its attempts)
+    status: np.ndarray       # [B] 0 reached t_bound, -1 step below 10 ulp(t), -2 error norm not finite
+    n_accepted: np.ndarray   # [B]
+    n_rejected: np.ndarray   # [B]
+    evals: int               # calls of fun
+    row_evals: int           # rows summed over those calls
+    history: list            # per row: its attempts in order, True accepted / False rejected
+
+
+class _TorchStages:
+    """The three per-element operations of an attempt with torch ops, on any device (the restatement that is
+    checked against scipy)."""
+
+    @staticmethod
+    def _rowvec(v, like):
+        return v.reshape(-1, *([1] * (like.dim() - 1)))
+
+    def combine(self, y, h, ks, coefs, want32):
+        out = y + _lincomb([k.to(y.dtype) for k in ks], coefs) * self._rowvec(h, y)
+        return out, (out.to(torch.complex64 if out.is_complex() else torch.float32) if want32 else None)
+
+    def rownorm(self, vs, coefs, a, b2, rtol, atol, m=None):
+        v = _lincomb([k.to(a.dtype) for k in vs], coefs)
+        if m is not None:
+            v = v * self._rowvec(m, a)
+        scale = atol + torch.maximum(a.abs(), b2.abs()) * rtol
+        q = (v / scale).abs().double().pow(2).reshape(a.shape[0], -1)
+        return torch.sqrt(q.sum(1) / q.shape[1])
+
+    def accept(self, mask, y, y_new, f, f_new):
+        idx = torch.nonzero(mask).flatten()
+        y[idx] = y_new[idx]
+        f[idx] = f_new[idx]
+
+
+class _HipStages:
+    """The same three operations on the kernels of csrc/ode.hip (device tensors only)."""
+
+    def combine(self, y, h, ks, coefs, want32):
+        from . import ops
+        return ops.rk45_combine(y, h, ks, coefs, want32)
+
+    def rownorm(self, vs, coefs, a, b2, rtol, atol, m=None):
+        from . import ops
+        return ops.rk45_rownorm(vs, coefs, a, b2, rtol, atol, m)
+
+    def accept(self, mask, y, y_new, f, f_new):
+        from . import ops
+        ops.rk45_accept(mask, y, y_new, f, f_new)
+
+
+def _upload(a: np.ndarray, dev):
+    """A small host array as a device tensor: pinned and non-blocking (train.FusedAdam.grad_table), so the
+    controller's per-attempt step sizes and masks do not synchronise."""
+    t = torch.from_numpy(np.ascontiguousarray(a))
+    if dev.type == "cpu":
+        return t
+    return t.pin_memory().to(dev, non_blocking=True)
+
+
+def rk45_solve_rows(fun, t0: float, t_bound: float, y0: torch.Tensor, rtol: float = 1e-3, atol: float = 1e-6,
+                    max_step: float = math.inf, first_step=None, clip_initial: bool = False, compact: bool = True,
+                    impl: str | None = None, cast32: bool = False) -> OdeRowsResult:
+    """rk45_solve for a batch of B independent ODEs y0 [B, ...] over one interval (t0, t_bound): the algorithm above
+    with every scalar of the controller per row -- t, h_abs, min_step = 10 ulp(t), the clip to t_bound, the
+    rejected-in-this-step flag, the initial step's three norms, FSAL, status and the counters.  One attempt advances
+    all live rows at once, each by its own h, so a row's trajectory is the sequence of its own attempts: what
+    rk45_solve gives it alone (nfev = 2 + 6 x its attempts).  A row that reaches t_bound (status 0) or falls below
+    min_step (-1) leaves the live set and the others go on; a row whose error norm is not finite leaves at once
+    with status -2 and a NaN state (rk45_solve would reject and shrink it some 50 times before min_step ends it).
+
+    fun(t, y, rows) -> dy/dt [b, ...] (float32 / complex64 or float64 / complex128; promotion is exact) for the b
+    rows being integrated: t float64 [b] and rows int64 [b] (their indices in y0) are HOST tensors -- the controller
+    keeps the times on the host, so a drift that needs per-row scalars computes them without a read-back --
+    and y [b, ...] is the state in the solver's dtype on y0's device.  cast32: fun is called as
+    fun(t, y, rows, y32) with y's float32 / complex64 cast (the HIP combine kernel writes it with the state, which
+    saves the network's input a pass).
+
+    compact=True evaluates fun on the live rows only (their state is gathered when a row leaves); compact=False
+    keeps finished rows in the batch with h = 0 (for tests).  impl "torch" runs the per-element work with torch ops
+    on any device; "hip" (the default for device tensors) on snrse_rk45_combine / _rownorm / _accept.  The
+    controller is host float64 either way: per attempt the live rows' error norms come back in one read-back (the
+    one synchronisation rk45_solve takes too) and h and the accept mask go up as small pinned arrays."""
+    if not (rtol > 0 and atol >= 0):
+        raise ValueError("rtol must be > 0 and atol >= 0")
+    if rtol < 100 * np.finfo(float).eps:
+        rtol = 100 * np.finfo(float).eps
+    if y0.dim() < 1 or y0.shape[0] == 0:
+        raise ValueError("rk45_solve_rows: y0 is [B, ...] with B >= 1")
+    dev = y0.device
+    if impl is None:
+        impl = "hip" if dev.type == "cuda" else "torch"
+    if impl not in ("torch", "hip"):
+        raise ValueError(f"rk45_solve_rows: impl {impl!r} (one of 'torch', 'hip')")
+    if impl == "hip" and dev.type != "cuda":
+        raise RuntimeError("rk45_solve_rows: impl='hip' needs HIP device tensors (no CPU fallback)")
+    st = _HipStages() if impl == "hip" else _TorchStages()
+    dtype = torch.complex128 if y0.is_complex() else torch.float64
+    dtype32 = torch.complex64 if y0.is_complex() else torch.float32
+    B = y0.shape[0]
+    t0, t_bound = float(t0), float(t_bound)
+    direction = float(np.sign(t_bound - t0)) if t_bound != t0 else 1.0
+
+    y_out = y0.to(dtype).contiguous().clone()        # finished rows' states, by original index
+    t_row = np.full(B, t0)
+    h_abs = np.zeros(B)
+    nfev = np.zeros(B, dtype=np.int64)
+    status = np.full(B, 1, dtype=np.int64)           # 1: still integrating
+    n_acc = np.zeros(B, dtype=np.int64)
+    n_rej = np.zeros(B, dtype=np.int64)
+    fresh = np.ones(B, dtype=bool)                   # the next attempt opens a step (min_step clip, rejected = False)
+    rejected = np.zeros(B, dtype=bool)
+    history = [[] for _ in range(B)]
+    evals = row_evals = 0
+
+    rows = np.arange(B)                              # original index of every row of the working state
+    y = y_out.clone()
+    y32 = y0.contiguous() if (cast32 and y0.dtype == dtype32) else (y.to(dtype32) if cast32 else None)
+
+    def f_eval(tt, yy, yy32):
+        nonlocal evals, row_evals
+        evals += 1
+        row_evals += len(rows)
+        nfev[rows[status[rows] == 1]] += 1
+        args = (torch.from_numpy(np.ascontiguousarray(tt, dtype=np.float64)), yy, torch.from_numpy(rows.copy()))
+        out = fun(*args, yy32) if cast32 else fun(*args)
+        if impl == "torch":
+            out = out.to(dtype)
+        return out.contiguous()
+
+    def retire(keep):
+        """Finished rows leave: their states go to y_out; with compact the working state is gathered to `keep`."""
+        nonlocal y, f, rows
+        gone = ~keep
+        if gone.any():
+            src = _upload(np.nonzero(gone)[0], dev)
+            y_out[_upload(rows[gone], dev)] = y[src]
+        if compact and gone.any():
+            idx = _upload(np.nonzero(keep)[0], dev)
+            y, f = y[idx].contiguous(), f[idx].contiguous()
+            rows = rows[keep]
+
+    f = f_eval(t_row, y, y32)
+    interval = abs(t_bound - t0)
+    if first_step is not None:
+        h_abs[:] = float(first_step)
+    elif clip_initial and interval == 0.0:
+        h_abs[:] = 0.0
+    else:
+        # select_initial_step per row: d0, d1 in one read-back, then the probe, then d2
+        d01 = torch.stack([st.rownorm([y], [1.0], y, y, rtol, atol), st.rownorm([f], [1.0], y, y, rtol, atol)]).cpu()
+        d0, d1 = d01[0].numpy(), d01[1].numpy()
+        h0 = np.empty(B)
+        for b in range(B):
+            h0[b] = 1e-6 if (d0[b] < 1e-5 or d1[b] < 1e-5) else 0.01 * float(d0[b]) / float(d1[b])
+            if clip_initial:
+                h0[b] = min(h0[b], interval)
+        y1, y1_32 = st.combine(y, _upload(h0 * direction, dev), [f], [1.0], cast32)
+        f1 = f_eval(t0 + h0 * direction, y1, y1_32)
+        d2 = st.rownorm([f1, f], [1.0, -1.0], y, y, rtol, atol).cpu().numpy()
+        for b in range(B):
+            d2b = float(d2[b]) / h0[b]
+            if d1[b] <= 1e-15 and d2b <= 1e-15:
+                h1 = max(1e-6, h0[b] * 1e-3)
+            else:
+                h1 = (0.01 / max(float(d1[b]), d2b)) ** (1 / (_ORDER + 1))
+            h_abs[b] = min(100 * h0[b], h1, interval, max_step) if clip_initial else min(100 * h0[b], h1)
+        del y1, y1_32, f1
+    if y[0].numel() == 0 or t0 == t_bound:
+        status[:] = 0
+
+    while True:
+        live = status[rows] == 1
+        if not live.any():
+            break
+        if compact and not live.all():
+            retire(live)
+            live = np.ones(len(rows), dtype=bool)
+        n = len(rows)
+        h = np.zeros(n)
+        t_new = t_row[rows].copy()
+        # open a step / check the retried one (RungeKutta._step_impl), row by row in Python floats
+        for i, r in enumerate(rows):
+            if not live[i]:
+                continue
+            t = float(t_row[r])
+            min_step = 10 * abs(np.nextafter(t, direction * np.inf) - t)
+            ha = float(h_abs[r])
+            if fresh[r]:
+                ha = max_step if ha > max_step else (min_step if ha < min_step else ha)
+                fresh[r] = False
+                rejected[r] = False
+            if ha < min_step:
+                status[r] = -1
+                live[i] = False
+                continue
+            hh = ha * direction
+            tn = t + hh
+            if direction * (tn - t_bound) > 0:
+                tn = t_bound
+            hh = tn - t
+            h[i], t_new[i], h_abs[r] = hh, tn, abs(hh)
+        if not live.any():
+            continue
+        if compact and not live.all():
+            retire(live)
+            h, t_new = h[live], t_new[live]
+            live = np.ones(len(rows), dtype=bool)
+        tr = t_row[rows]
+        h_dev = _upload(h, dev)
+        K = [f]
+        for s in range(1, 6):
+            ys, ys32 = st.combine(y, h_dev, K, _A[s], cast32)
+            K.append(f_eval(tr + _C[s] * h, ys, ys32))
+        y_new, y_new32 = st.combine(y, h_dev, K, _B, cast32)
+        f_new = f_eval(tr + h, y_new, y_new32)
+        K.append(f_new)
+        err_all = st.rownorm(K, _E, y, y_new, rtol, atol, m=h_dev).cpu().numpy()  # the attempt's one synchronisation
+        mask = np.zeros(len(rows), dtype=np.int32)
+        bad = np.zeros(len(rows), dtype=bool)
+        for i, r in enumerate(rows):
+            if not live[i]:
+                continue
+            err = float(err_all[i])
+            ha = float(h_abs[r])
+            if not math.isfinite(err):
+                status[r] = -2
+                bad[i] = True
+                continue
+            if err < 1:
+                factor = MAX_FACTOR if err == 0 else min(MAX_FACTOR, SAFETY * err ** _EXP)
+                if rejected[r]:
+                    factor = min(1.0, factor)
+                h_abs[r] = ha * factor
+                n_acc[r] += 1
+                history[r].append(True)
+                mask[i] = 1
+                fresh[r] = True
+                t_row[r] = t_new[i]
+                if direction * (t_new[i] - t_bound) >= 0:
+                    status[r] = 0
+            else:
+                h_abs[r] = ha * max(MIN_FACTOR, SAFETY * err ** _EXP)
+                rejected[r] = True
+                n_rej[r] += 1
+                history[r].append(False)
+        if mask.any():
+            st.accept(_upload(mask, dev), y, y_new, f, f_new)
+        if bad.any():
+            y[_upload(np.nonzero(bad)[0], dev)] = complex("nan+nanj") if y.is_complex() else float("nan")
+    retire(np.zeros(len(rows), dtype=bool))
+    return OdeRowsResult(y=y_out, t=t_row, nfev=nfev, status=status, n_accepted=n_acc, n_rejected=n_rej, evals=evals,
+                         row_evals=row_evals, history=history)

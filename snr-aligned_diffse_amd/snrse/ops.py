@@ -726,6 +726,88 @@ def range_stats(t, peak=None, nonfinite=None, accumulate=False):
     return peak, nonfinite
 
 
+_RK45_DT = {torch.float32: F32, torch.complex64: F32, torch.float64: _lib.F64, torch.complex128: _lib.F64}
+
+
+def _rk45_rows(y):
+    """(B, doubles per row) of a contiguous float64 / complex128 [B, ...] state."""
+    if y.dtype not in (torch.float64, torch.complex128) or not y.is_contiguous() or y.dim() < 1 or y.numel() == 0:
+        raise TypeError("snrse: the RK45 kernels take a contiguous, non-empty float64 / complex128 [B, ...] state")
+    B = y.shape[0]
+    return B, (y.numel() // B) * (2 if y.is_complex() else 1)
+
+
+def _rk45_stages(ks, coefs, like):
+    """Stage tensors and coefficients as snrse_rk45_* take them: zero coefficients dropped (ode._lincomb), one
+    dtype, the state's shape and complexness -> (pointer array, coefficient array, ns, dtype code, kept tensors)."""
+    kept = [(k, float(c)) for k, c in zip(ks, coefs) if float(c) != 0.0]
+    if len(kept) > 7:
+        raise ValueError("snrse: at most 7 stages")
+    for k, _ in kept:
+        if (k.dtype not in _RK45_DT or k.dtype != kept[0][0].dtype or k.shape != like.shape
+                or k.is_complex() != like.is_complex() or not k.is_contiguous()):
+            raise TypeError("snrse: RK45 stages are contiguous tensors of the state's shape, all float32 / complex64 "
+                            "or all float64 / complex128")
+    _dev(like, *[k for k, _ in kept])
+    ns = len(kept)
+    ptrs = (C.c_void_p * max(ns, 1))(*[k.data_ptr() for k, _ in kept])
+    cs = (C.c_double * max(ns, 1))(*[c for _, c in kept])
+    return ptrs, cs, ns, (_RK45_DT[kept[0][0].dtype] if kept else _lib.F64), [k for k, _ in kept]
+
+
+def rk45_combine(y, h, ks, coefs, want32=False):
+    """out[b] = y[b] + h[b] * (sum_s coefs[s] ks[s][b]) in float64, stage order, every product and sum rounded on
+    its own (snrse_rk45_combine).  y: float64 / complex128 [B, ...]; h: float64 [B] on the device; ks: float32 /
+    complex64 or float64 / complex128 tensors shaped like y.  Returns (out, out32): out32 is out cast to
+    float32 / complex64 when want32, else None."""
+    B, n = _rk45_rows(y)
+    if h.dtype != torch.float64 or h.numel() != B or not h.is_contiguous():
+        raise TypeError(f"snrse: rk45_combine takes h as {B} contiguous float64 values")
+    ptrs, cs, ns, dt, _keep = _rk45_stages(ks, coefs, y)
+    _dev(y, h)
+    out = torch.empty_like(y)
+    out32 = torch.empty_like(y, dtype=torch.complex64 if y.is_complex() else torch.float32) if want32 else None
+    _lib.call("snrse_rk45_combine", y.data_ptr(), h.data_ptr(), ptrs, cs, ns, dt, B, n, out.data_ptr(), _ptr(out32),
+              _stream())
+    return out, out32
+
+
+def rk45_rownorm(vs, coefs, a, b2, rtol, atol, m=None):
+    """[B] float64: sqrt(mean_e |m[b] sum_s coefs[s] vs[s][b, e]|^2 / (atol + rtol max(|a|, |b2|))^2) per row, the
+    modulus complex when the state is (snrse_rk45_rownorm: block partials, then a fold in a fixed order -- the same
+    bits on every launch).  m: float64 [B] on the device, or None for 1."""
+    B, n = _rk45_rows(a)
+    if b2.dtype != a.dtype or b2.shape != a.shape or not b2.is_contiguous():
+        raise TypeError("snrse: rk45_rownorm takes a and b2 of one shape and dtype")
+    if m is not None and (m.dtype != torch.float64 or m.numel() != B or not m.is_contiguous()):
+        raise TypeError(f"snrse: rk45_rownorm takes m as {B} contiguous float64 values")
+    ptrs, cs, ns, dt, _keep = _rk45_stages(vs, coefs, a)
+    _dev(a, b2, m)
+    bpr = _lib.load().snrse_rk45_rownorm_blocks(B, n)
+    partial = torch.empty(B, bpr, device=a.device, dtype=torch.float64)
+    out = torch.empty(B, device=a.device, dtype=torch.float64)
+    _lib.call("snrse_rk45_rownorm", ptrs, cs, ns, dt, _ptr(m), a.data_ptr(), b2.data_ptr(), float(rtol), float(atol),
+              int(a.is_complex()), B, n, partial.data_ptr(), out.data_ptr(), _stream())
+    return out
+
+
+def rk45_accept(mask, y, y_new, f, f_new):
+    """In place, for the rows with mask[b] != 0 (int32 [B] on the device): y[b] <- y_new[b], f[b] <- f_new[b]; the
+    other rows keep their bits (snrse_rk45_accept)."""
+    B, n = _rk45_rows(y)
+    if y_new.dtype != y.dtype or y_new.shape != y.shape or not y_new.is_contiguous():
+        raise TypeError("snrse: rk45_accept takes y and y_new of one shape and dtype")
+    if (f.dtype not in _RK45_DT or f_new.dtype != f.dtype or f.shape != y.shape or f_new.shape != y.shape
+            or not (f.is_contiguous() and f_new.is_contiguous())):
+        raise TypeError("snrse: rk45_accept takes f and f_new of the state's shape and one dtype")
+    if mask.dtype != torch.int32 or mask.numel() != B or not mask.is_contiguous():
+        raise TypeError(f"snrse: rk45_accept takes the mask as {B} contiguous int32 values")
+    _dev(mask, y, y_new, f, f_new)
+    fwords = (f.numel() // B) * f.element_size() // 4
+    _lib.call("snrse_rk45_accept", mask.data_ptr(), y.data_ptr(), y_new.data_ptr(), 2 * n, f.data_ptr(),
+              f_new.data_ptr(), fwords, B, _stream())
+
+
 def stft(sig, in_scale=1.0, tpad=None, mode=1, in_div=None, lengths=None):
     """sig [B, L] f32 -> complex64 [B, 256, Tpad] of sig * in_scale / in_div[b].  lengths: ragged batch, row b
     reflects at its own L_b, has 1 + L_b // 128 frames and zeros after them; a row of 255 samples or fewer (too

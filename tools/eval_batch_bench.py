@@ -9,7 +9,12 @@ Models (formula weights): the fp16 PC sampler at N = 30 (`bbed`) and the fp16 SN
 (`sebridge_v3`, SNRNet estimate).  Writes both times, the speed-up, the plan's batch-size histogram and the
 largest per-file difference between the two modes' waveforms to profiles/eval_batch.json.
 
+`--models ode` is the probability-flow ODE leg (fp16 `bbed`, rtol = atol = 1e-3): the per-file enhance() loop against
+enhance_batch's per-row adaptive RK45, three runs each, interleaved; files/s of both with their spread, the batch
+utilisation row_evals / (evals x B) and the per-file nfev range go to profiles/eval_batch_ode.json.
+
     python tools/eval_batch_bench.py [--clips 64] [--batch-size 32] [--N 30] [--rounds 2] [--out profiles/eval_batch.json]
+    python tools/eval_batch_bench.py --models ode [--ode-tol 1e-3] [--ode-rounds 3] [--ode-out profiles/eval_batch_ode.json]
 """
 from __future__ import annotations
 
@@ -138,6 +143,57 @@ def bench_model(name, model, data, kw, args):
     return res
 
 
+def bench_ode(model, data, args):
+    """The ODE leg: the per-file enhance(sampler_type="ode") loop (the path before the batched route, untouched by
+    it) against enhance_batch's per-row RK45 at --batch-size, --ode-rounds runs each, interleaved A B A B A B.  The
+    two legs draw different priors (torch's generator / per-file Philox seeds), so only throughput is compared."""
+    kw = dict(sampler_type="ode", rtol=args.ode_tol, atol=args.ode_tol)
+    n = len(data)
+    res = {"model": "ode_rk45", "rtol": args.ode_tol, "atol": args.ode_tol, "loop_s": [], "batched_s": []}
+    torch.manual_seed(1)
+    run_loop(model, data[:2], kw)
+    run_batched(model, data[:2], kw, args.batch_size, args.max_frames)
+    stats = plan = None
+    for _ in range(args.ode_rounds):
+        torch.manual_seed(7)
+        t, _r = timed(lambda: run_loop(model, data, kw))
+        res["loop_s"].append(round(t, 3))
+        print(f"ode: loop {res['loop_s'][-1]} s", flush=True)
+        torch.manual_seed(7)
+        stats = []
+
+        def batched():
+            # enhance_batch is called once per planned batch: collect each call's solver statistics
+            from snrse import batching, evaluate
+            seeds = [int(torch.randint(0, 2 ** 62, (1,)).item()) for _ in data]
+            pl = batching.plan_batches([len(y) for _, y in data], args.batch_size, args.max_frames)
+            for b in pl:
+                hs = model.enhance_batch([data[i][1] for i in b], seeds=[seeds[i] for i in b], batch_size=len(b),
+                                         max_frames=args.max_frames, **kw)
+                evaluate.score_batch(hs, [data[i][0] for i in b], [data[i][1] for i in b])
+                stats.extend(model.last_ode_stats)
+            return pl
+
+        t, plan = timed(batched)
+        res["batched_s"].append(round(t, 3))
+        print(f"ode: batch_size {args.batch_size} {res['batched_s'][-1]} s", flush=True)
+    lf = [n / t for t in res["loop_s"]]
+    bf = [n / t for t in res["batched_s"]]
+    res["loop_files_per_s"] = [round(v, 3) for v in lf]
+    res["batched_files_per_s"] = [round(v, 3) for v in bf]
+    res["loop_spread_files_per_s"] = round(max(lf) - min(lf), 3)
+    res["batched_spread_files_per_s"] = round(max(bf) - min(bf), 3)
+    res["speedup_median"] = round(float(np.median(bf) / np.median(lf)), 2)
+    res["batched_faster_beyond_spread"] = bool(min(bf) - max(lf) > max(max(lf) - min(lf), max(bf) - min(bf)))
+    nfev = [v for s in stats for v in s["nfev"]]
+    res["nfev_min"], res["nfev_max"], res["nfev_mean"] = min(nfev), max(nfev), round(float(np.mean(nfev)), 1)
+    res["utilisation"] = round(sum(s["row_evals"] for s in stats) / sum(s["evals"] * len(s["files"]) for s in stats), 3)
+    hist = collections.Counter(len(b) for b in plan)
+    res["batches"] = len(plan)
+    res["batch_size_histogram"] = {str(k): hist[k] for k in sorted(hist)}
+    return res
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--clips", type=int, default=64)
@@ -146,8 +202,11 @@ def main(argv=None):
     ap.add_argument("--N", type=int, default=30)
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--dtype", default="fp16")
-    ap.add_argument("--models", default="pc,snr")
+    ap.add_argument("--models", default="pc,snr", help="comma list of pc, snr, ode")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "eval_batch.json"))
+    ap.add_argument("--ode-tol", type=float, default=1e-3, help="rtol = atol of the ODE leg")
+    ap.add_argument("--ode-rounds", type=int, default=3)
+    ap.add_argument("--ode-out", default=os.path.join(ROOT, "profiles", "eval_batch_ode.json"))
     args = ap.parse_args(argv)
     from sgmse.model import set_snr_model
     data = clips(args.clips)
@@ -163,6 +222,17 @@ def main(argv=None):
         m, keys = formula_model("sebridge_v3", "true", args.dtype, fixed_snr=0.17783)
         set_snr_model(formula_snr_estimator(keys))
         out["results"].append(bench_model("snr_aligned_one_step", m, data, dict(sampler_type="pc", N=args.N), args))
+    if "ode" in args.models.split(","):
+        m, _ = formula_model("bbed", "false", args.dtype)
+        ode = dict({k: v for k, v in out.items() if k != "results"}, results=[bench_ode(m, data, args)])
+        os.makedirs(os.path.dirname(os.path.abspath(args.ode_out)), exist_ok=True)
+        with open(args.ode_out, "w") as f:
+            json.dump(ode, f, indent=1)
+            f.write("\n")
+        print(json.dumps(ode))
+        del m
+    if not out["results"]:
+        return
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(out, f, indent=1)
