@@ -290,6 +290,22 @@ int snrse_absmax_ragged(const float* sig, const int* lengths, int B, int Lstride
 int snrse_stft_ragged(const float* sig, const int* lengths, int B, int Lstride, const float* in_div,
                       float in_scale, int Tpad, int mode, void* out, hipStream_t stream);
 
+/* Sample-rate conversion in front of the network (csrc/audio_resample.hip): rational polyphase FIR resampling of a
+ * ragged batch, x [B][stride_in] f32 with lengths [B] int32 on the device -> y [B][stride_out] f32.  The
+ * arithmetic of scipy.signal.resample_poly(x, up, down, window=w, padtype='constant'): with half = (len(w) - 1) / 2,
+ * h = up w and n_out_b = ceil(L_b up / down),
+ *   y[b][m] = sum_n x[b][n] h[m down + half - n up]     0 <= n < L_b,  0 <= m down + half - n up <= 2 half.
+ * up, down must be coprime.  taps: h phase-major, [up][K] f32 with K = ceil((2 half + 1) / up) and
+ * taps[p][j] = h[p + j up] (0 where p + j up > 2 half); NULL is allowed for up == down == 1, which copies.
+ * Nothing at or past L_b of a row is read, outputs [n_out_b, stride_out) are written as zero, L_b = 0 gives a row
+ * of zeros; the CALLER sees to n_out_b <= stride_out (an output past the stride is not written).  Every output is
+ * one fp32 fma chain over j ascending: no atomics, the same bits on every launch and for a row launched alone.
+ * EINVAL when a block's input span, about 256 down / up + K samples, exceeds 64 KB of LDS (down / up above ~60).
+ * snrse_resample_poly_block: outputs per block (the lengths at which the kernel changes path). */
+int snrse_resample_poly(const float* x, const int* lengths, int B, long long stride_in, int up, int down, int half,
+                        const float* taps, float* y, long long stride_out, hipStream_t stream);
+int snrse_resample_poly_block(void);
+
 /* Range statistics of a contiguous tensor [B][per] (dtype SNRSE_F32 / SNRSE_F16 / SNRSE_BF16; a complex64
  * spectrogram is 2*per floats): peak[b] = max |v| over the FINITE elements of row b (0 when there is none),
  * nonfinite[b] = number of inf / NaN elements of row b (saturating at INT_MAX).  accumulate == 0: overwrite

@@ -367,7 +367,8 @@ class ScoreModel(nn.Module):
     @torch.no_grad()
     def enhance_batch(self, ys, seeds=None, batch_size=32, max_frames=16384, sampler_type="pc",
                       predictor="reverse_diffusion", corrector="ald", N=30, corrector_steps=1, snr=0.5, oracle=False,
-                      clean_rms=None, noise_rms=None, range_guard="auto", **kwargs):
+                      clean_rms=None, noise_rms=None, range_guard="auto", sample_rates=None, output_rate="model",
+                      **kwargs):
         """enhance() for a list of noisy utterances of different lengths (each [L], [1, L], numpy or tensor) ->
         list of numpy [L_i] in input order.  Utterances whose spectrograms pad to the same frame count share a
         ragged batch (snrse.batching.plan_batches: at most batch_size rows and max_frames frames per batch).
@@ -386,11 +387,37 @@ class ScoreModel(nn.Module):
         and correct_stepsize are accepted and ignored).  Its prior is drawn from the per-utterance Philox seeds
         like the PC route's, so the results do not depend on batch_size -- but they are a different noise
         realisation from a loop over enhance(sampler_type="ode"), whose prior comes from torch's device
-        generator (sde.prior_sampling)."""
+        generator (sde.prior_sampling).
+
+        sample_rates: None (every utterance is at the model's 16 kHz; output_rate is not looked at), or one rate per
+        utterance: those not at 16 kHz are resampled on the device first (snrse.resample.convert: one ragged
+        ops.resample_poly launch per distinct rate), and everything above -- the batch plan, max|y|, the results'
+        lengths -- is that of the 16 kHz signals, resampled_length(L_i, rate_i, 16000) samples each.  The seeds
+        are drawn as without it, before any device work.  output_rate "model" returns the 16 kHz waveforms,
+        "input" resamples each back to its own rate and cuts it to exactly L_i samples."""
         from snrse import batching
         from snrse.enhance import ODEEnhancer, PCEnhancer, SNRAlignedEnhancer
         n = len(ys)
         route = self._batch_route(sampler_type, corrector, kwargs)
+        if sample_rates is not None:
+            from snrse import audio, resample
+            if output_rate not in ("model", "input"):
+                raise ValueError(f"enhance_batch: output_rate is 'model' or 'input', got {output_rate!r}")
+            if len(sample_rates) != n:
+                raise ValueError(f"enhance_batch: {len(sample_rates)} sample rates for {n} utterances")
+            if seeds is None and route is not None:
+                seeds = [_noise_seed() for _ in range(n)]
+            lens_in = [int(resample.as_signal(y).numel()) for y in ys]
+            # the batched enhancers gather their ragged batches on the device, where the resampled rows already are
+            ys16 = resample.convert(ys, sample_rates, audio.MODEL_RATE, on_device=route is not None)
+            out = self.enhance_batch(ys16, seeds=seeds, batch_size=batch_size, max_frames=max_frames,
+                                     sampler_type=sampler_type, predictor=predictor, corrector=corrector, N=N,
+                                     corrector_steps=corrector_steps, snr=snr, oracle=oracle, clean_rms=clean_rms,
+                                     noise_rms=noise_rms, range_guard=range_guard, **kwargs)
+            if output_rate == "input":
+                back = resample.convert(out, audio.MODEL_RATE, sample_rates)
+                out = [np.asarray(h)[:L] for h, L in zip(back, lens_in)]
+            return out
         if route is None:
             out = []
             for i, y in enumerate(ys):
@@ -433,7 +460,8 @@ class ScoreModel(nn.Module):
             ode_stats = self.last_ode_stats = []
             for rows in plan:
                 stride = max(lens[i] for i in rows)
-                buf = torch.zeros(len(rows), stride, dtype=torch.float32)
+                on_dev = sigs[rows[0]].is_cuda  # rows resampled on the device (sample_rates): all of them are there
+                buf = torch.zeros(len(rows), stride, dtype=torch.float32, device=dev if on_dev else None)
                 for r, i in enumerate(rows):
                     buf[r, :lens[i]] = sigs[i]
                 yb = buf.to(dev)

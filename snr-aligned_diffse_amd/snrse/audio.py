@@ -9,6 +9,7 @@ anything else raises ValueError.  The file is memory-mapped and decoded with one
 """
 from __future__ import annotations
 
+import math
 import struct
 
 import numpy as np
@@ -48,10 +49,22 @@ def _layout(path: str):
     return raw, fmt, data[0], data[1] // align
 
 
+FORMATS = {(_PCM, 8), (_PCM, 16), (_PCM, 24), (_PCM, 32), (_FLOAT, 32), (_FLOAT, 64)}  # (tag, bits) read_wav decodes
+
+
 def info(path: str):
     """-> (frames, channels, sample_rate) from the headers alone: what load(path)'s tensor shape will be."""
     _, fmt, _, n = _layout(path)
     return n, fmt[1], fmt[2]
+
+
+def readable(path: str) -> bool:
+    """Whether load(path) can decode the file, from its headers alone."""
+    try:
+        fmt = _layout(path)[1]
+    except (ValueError, OSError, struct.error):
+        return False
+    return (fmt[0], fmt[5]) in FORMATS
 
 
 def read_wav(path: str):
@@ -83,6 +96,37 @@ def load(path: str):
     """torchaudio.load(path) equivalent -> (float32 tensor [channels, frames], sample_rate)."""
     x, sr = read_wav(path)
     return torch.from_numpy(np.ascontiguousarray(x.T)), sr
+
+
+MODEL_RATE = 16000  # the sample rate the networks were trained at
+
+
+def rational(sr_in: int, sr_out: int):
+    """-> (up, down), sr_out / sr_in in lowest terms: what ops.resample_poly takes to go from sr_in to sr_out."""
+    sr_in, sr_out = int(sr_in), int(sr_out)
+    if sr_in <= 0 or sr_out <= 0:
+        raise ValueError(f"sample rates must be positive, got {sr_in} -> {sr_out}")
+    g = math.gcd(sr_in, sr_out)
+    return sr_out // g, sr_in // g
+
+
+def resampled_length(L: int, sr_in: int, sr_out: int) -> int:
+    """Samples ops.resample_poly returns for L samples at sr_in brought to sr_out: ceil(L up / down), as
+    scipy.signal.resample_poly.  From the numbers alone, so a batch can be planned from WAV headers (info)."""
+    up, down = rational(sr_in, sr_out)
+    return -((-int(L) * up) // down)
+
+
+def resample_taps(up: int, down: int) -> np.ndarray:
+    """scipy.signal.resample_poly's default filter w for coprime (up, down), float64 [2 half + 1] with
+    half = 10 max(up, down): firwin(2 half + 1, 1 / max(up, down), window=('kaiser', 5.0)) restated in numpy
+    (fc sinc(fc n) times the Kaiser window, normalised to sum 1).  The resampler applies h = up w."""
+    mx = max(int(up), int(down))
+    half = 10 * mx
+    n = np.arange(-half, half + 1, dtype=np.float64)
+    fc = 1.0 / mx
+    w = fc * np.sinc(fc * n) * np.kaiser(2 * half + 1, 5.0)
+    return w / w.sum()
 
 
 def write_wav(path: str, x: np.ndarray, sr: int = 16000, bits: int = 16):

@@ -37,7 +37,7 @@ import numpy as np
 import torch
 
 from . import audio, dist as sdist, ops
-from .evaluate import _pesq_fn, print_mean_std, sdist_backend_is_nccl
+from .evaluate import _pesq_fn, load_pair, print_mean_std, sdist_backend_is_nccl
 
 SNRS = tuple(range(0, 41, 5))  # deep_eval.py:112
 LABELS = tuple(s - 5 for s in SNRS)
@@ -115,9 +115,11 @@ def enhance_variants(model, ys, noise_rms, clean_rms=1.0, sampler_type="pc", pre
 def deep_evaluate(model, test_dir, target_dir, sampler_type="pc", predictor="reverse_diffusion", corrector="ald",
                   corrector_steps=1, snr=0.5, N=30, reverse_starting_point=1.0, force_N=0, atol=1e-5, rtol=1e-5,
                   timestep_type="linear", correct_stepsize=True, oracle=False, rank=0, world=1, batched=True,
-                  si_sdr=False, noise_tapes=None, verbose=True):
+                  si_sdr=False, noise_tapes=None, verbose=True, resample=False):
     """-> dict: 'filename' and 'pesq_<label>' (+ 'si_sdr_<label>') lists over all files (every rank).
-    noise_tapes(file_index) -> noise_tape for that file's batch (parity runs)."""
+    noise_tapes(file_index) -> noise_tape for that file's batch (parity runs).  resample: clean / noisy files that
+    are not at 16 kHz are brought to it on the device as they are loaded (snrse.evaluate.load_pair); without it the
+    rate is not looked at."""
     clean_dir, noisy_dir = join(test_dir, "clean"), join(test_dir, "noisy")
     for lab in LABELS:
         os.makedirs(join(target_dir, "{0:02d}".format(lab)), exist_ok=True)
@@ -136,8 +138,7 @@ def deep_evaluate(model, test_dir, target_dir, sampler_type="pc", predictor="rev
     run = [0.0] * len(LABELS)
     for cnt, i in enumerate(range(a, b)):
         name = os.path.basename(files[i])
-        x, sr = audio.load(join(clean_dir, name))
-        y, _ = audio.load(files[i])
+        x, y, sr = load_pair(join(clean_dir, name), files[i], resample)
         x, y = x[0].numpy(), y[0].numpy()
         ys, noise_rms = snr_variants(x, y)
         xh = enhance_variants(model, ys, noise_rms, 1.0, sampler_type=sampler_type, predictor=predictor,
@@ -215,6 +216,8 @@ def main(argv=None):
     ap.add_argument("--oracle", action="store_true", help="SNR oracle (deep_eval.py's --oracle)")
     ap.add_argument("--per_variant", action="store_true", help="the reference's B=1 loop instead of one batch")
     ap.add_argument("--si_sdr", action="store_true")
+    ap.add_argument("--resample", action="store_true",
+                    help="bring clean / noisy files that are not at 16 kHz to 16 kHz on the device first")
     ap.set_defaults(correct_stepsize=True)
     a = ap.parse_args(argv)
     rank, world, _ = sdist.init_from_env()
@@ -226,7 +229,7 @@ def main(argv=None):
                   corrector=a.corrector, corrector_steps=a.corrector_steps, snr=a.snr, N=a.N,
                   reverse_starting_point=a.reverse_starting_point, force_N=a.force_N, atol=a.atol, rtol=a.rtol,
                   timestep_type=a.timestep_type, correct_stepsize=a.correct_stepsize, oracle=a.oracle,
-                  rank=rank, world=world, batched=not a.per_variant, si_sdr=a.si_sdr)
+                  rank=rank, world=world, batched=not a.per_variant, si_sdr=a.si_sdr, resample=a.resample)
 
 
 if __name__ == "__main__":

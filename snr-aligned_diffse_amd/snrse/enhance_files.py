@@ -1,0 +1,146 @@
+"""Enhance a folder of noisy recordings: no clean reference, any sample rate, any channel count.
+
+Every *.wav of <noisy_dir> that snrse.audio can read (sorted by name) is taken; every channel of a file is one
+utterance with a noise seed of its own.  The utterances are planned from the WAV headers alone (their lengths at
+16 kHz, snrse.audio.resampled_length), grouped into ragged batches as snrse.evaluate --batch_size does
+(snrse.batching.plan_batches), and each batch is one ScoreModel.enhance_batch(sample_rates=...) call: channels that
+are not at 16 kHz are resampled on the device (snrse_resample_poly), everything runs through the ragged-batch
+enhancers, so the range guard, --sampler_type ode and the one-step route come with it.  The channels are put back
+into a 16-bit PCM file of the same name and channel count under <destination_folder>: at 16 kHz, or with
+--output_rate input at the file's own rate and frame count.  _enhanced.csv lists name, input rate, channels,
+seconds and output rate of every file.
+
+The seeds are drawn first, one torch.randint(0, 2**62) per (file, channel), in file order then channel order: for
+a folder of 16 kHz mono files these are the draws, the plan and the calls of snrse.evaluate --batch_size B, and the
+files written are byte for byte those it writes into <destination_folder>/all.  Files shard contiguously over
+ranks (snrse.dist.shard_range); rank 0 writes the csv, which needs the headers only.
+
+    python -m snrse.enhance_files --noisy_dir DIR --ckpt CKPT --destination_folder OUT \\
+        [--batch_size 32] [--output_rate model|input] [--seed S] [--N 30 --sampler_type pc ...]
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import warnings
+from glob import glob
+from os.path import join
+
+import numpy as np
+import torch
+
+from . import audio, dist as sdist
+
+CSV_COLUMNS = ("filename", "input_rate", "channels", "seconds", "output_rate")
+
+
+def list_files(noisy_dir):
+    """-> [(path, frames, channels, rate)] of the readable *.wav files of noisy_dir, sorted; the others are named
+    in a warning and left out."""
+    out = []
+    for f in sorted(glob(join(noisy_dir, "*.wav"))):
+        if not audio.readable(f):
+            warnings.warn(f"enhance_files: skipping {f}: not a WAVE file snrse.audio reads")
+            continue
+        out.append((f, *audio.info(f)))
+    return out
+
+
+def utterances(files):
+    """[(file index, channel)] in file order then channel order: one utterance, one seed each."""
+    return [(k, c) for k, (_, _, ch, _) in enumerate(files) for c in range(ch)]
+
+
+def draw_seeds(n):
+    """n draws of the evaluation driver's per-file seed, in order."""
+    return [int(torch.randint(0, 2 ** 62, (1,)).item()) for _ in range(n)]
+
+
+def write_csv(files, output_rate, target_dir):
+    with open(join(target_dir, "_enhanced.csv"), "w") as f:
+        f.write(",".join(CSV_COLUMNS) + "\n")
+        for path, n, ch, sr in files:
+            ro = sr if output_rate == "input" else audio.MODEL_RATE
+            f.write(f"{os.path.basename(path)},{sr},{ch},{n / sr!r},{ro}\n")
+
+
+def enhance_files(model, noisy_dir, target_dir, batch_size=32, max_frames=16384, output_rate="model", rank=0,
+                  world=1, sampler_type="pc", predictor="reverse_diffusion", corrector="ald", corrector_steps=1,
+                  snr=0.5, N=30, reverse_starting_point=1.0, force_N=0, atol=1e-5, rtol=1e-5,
+                  timestep_type="linear", correct_stepsize=False, **enhance_kw):
+    """-> the list_files() rows of every file (all ranks'); this rank's share is enhanced and written."""
+    from .batching import plan_batches
+    if output_rate not in ("model", "input"):
+        raise ValueError(f"enhance_files: output_rate is 'model' or 'input', got {output_rate!r}")
+    os.makedirs(target_dir, exist_ok=True)
+    if model.sde.__class__.__name__ == "OUVESDE":  # as evaluate (eval.py:105-108)
+        model.sde._T = reverse_starting_point
+    else:
+        model.sde.T = reverse_starting_point
+    N = int(reverse_starting_point / (1 / N))
+    if force_N:
+        N = force_N
+    files = list_files(noisy_dir)
+    a, b = sdist.shard_range(len(files), rank, world)
+    mine = files[a:b]
+    utts = utterances(mine)
+    kw = dict(sampler_type=sampler_type, predictor=predictor, corrector=corrector, corrector_steps=corrector_steps,
+              N=N, snr=snr, atol=atol, rtol=rtol, timestep_type=timestep_type, correct_stepsize=correct_stepsize,
+              **enhance_kw)
+    # settings without a batched enhancer run enhance_batch's per-utterance loop, which draws as it goes
+    seeds = draw_seeds(len(utts)) if model._batch_route(sampler_type, corrector, enhance_kw) is not None else None
+    lens = [audio.resampled_length(mine[k][1], mine[k][3], audio.MODEL_RATE) for k, _ in utts]
+    done = {k: [None] * f[2] for k, f in enumerate(mine)}
+    for batch in plan_batches(lens, batch_size, max_frames):
+        loaded = {}
+        for u in batch:
+            k = utts[u][0]
+            if k not in loaded:
+                loaded[k] = audio.load(mine[k][0])[0]
+        hs = model.enhance_batch([loaded[utts[u][0]][utts[u][1]] for u in batch],
+                                 seeds=None if seeds is None else [seeds[u] for u in batch], batch_size=len(batch),
+                                 max_frames=max_frames, sample_rates=[mine[utts[u][0]][3] for u in batch],
+                                 output_rate=output_rate, **kw)
+        for u, h in zip(batch, hs):
+            k, c = utts[u]
+            done[k][c] = np.asarray(h, np.float32)
+            if all(v is not None for v in done[k]):
+                path, _, ch, sr = mine[k]
+                x = done.pop(k)
+                audio.write_wav(join(target_dir, os.path.basename(path)), x[0] if ch == 1 else np.stack(x, 1),
+                                sr if output_rate == "input" else audio.MODEL_RATE, bits=16)
+    if rank == 0:
+        write_csv(files, output_rate, target_dir)
+    return files
+
+
+def parser():
+    from .evaluate import sampler_arguments
+    ap = argparse.ArgumentParser(description="enhance a folder of noisy recordings on the MI355X path")
+    ap.add_argument("--noisy_dir", type=str, required=True)
+    ap.add_argument("--ckpt", type=str, required=True)
+    ap.add_argument("--destination_folder", type=str, required=True)
+    ap.add_argument("--batch_size", type=int, default=32, help="utterances (file channels) per ragged batch")
+    ap.add_argument("--output_rate", type=str, choices=("model", "input"), default="model",
+                    help="write at 16 kHz (model) or at each file's own rate and frame count (input)")
+    ap.add_argument("--seed", type=int, default=None, help="torch.manual_seed before the noise seeds are drawn")
+    sampler_arguments(ap)
+    return ap
+
+
+def main(argv=None):
+    from .evaluate import sampler_kwargs
+    a = parser().parse_args(argv)
+    rank, world, _ = sdist.init_from_env()
+    from sgmse.model import ScoreModel
+    model = ScoreModel.load_from_checkpoint(a.ckpt, base_dir="", batch_size=16, num_workers=0, kwargs=dict(gpu=False))
+    model.eval(no_ema=False)
+    model.cuda()
+    if a.seed is not None:
+        torch.manual_seed(a.seed)
+    enhance_files(model, a.noisy_dir, a.destination_folder, batch_size=a.batch_size, output_rate=a.output_rate,
+                  rank=rank, world=world, **sampler_kwargs(a))
+
+
+if __name__ == "__main__":
+    main()

@@ -20,6 +20,10 @@ B = 1, is the per-file loop.  With --sampler_type ode a batch integrates every f
 steps (snrse.enhance.ODEEnhancer); there B > 1 takes the prior from the per-file seeds, B = 1 from torch's device
 generator, so the two are different noise realisations.
 
+--resample: clean and noisy files whose header rate is not 16 kHz are brought to 16 kHz on the device
+(snrse.resample.convert, the polyphase kernel snrse_resample_poly) as they are loaded; the enhancement, the written
+files, the scoring and PESQ's rate are then those of 16 kHz signals.  Without the flag the rate is not looked at.
+
     python -m snrse.evaluate --test_dir DIR --ckpt CKPT --destination_folder OUT [--N 30 --batch_size 32 ...]
 """
 from __future__ import annotations
@@ -70,10 +74,25 @@ def score_files(x_hat, x, y, sr=16000, pesq_fn=None):
     return [p, float(er[0]), float(er[1]), float(er[2])]
 
 
+def load_pair(clean_path, noisy_path, resample=False):
+    """-> (x [channels, L], y [channels, L], sample rate) of one clean / noisy pair.  resample: a file whose rate is
+    not 16 kHz is brought to it on the device, every channel a row of the one launch, and the rate returned is
+    16000."""
+    x, sr = audio.load(clean_path)
+    y, sry = audio.load(noisy_path)
+    if resample and (sr != audio.MODEL_RATE or sry != audio.MODEL_RATE):
+        from .resample import convert
+        rows = convert(list(x) + list(y), [sr] * len(x) + [sry] * len(y), audio.MODEL_RATE)
+        x = torch.stack([torch.as_tensor(r) for r in rows[:len(x)]])
+        y = torch.stack([torch.as_tensor(r) for r in rows[len(x):]])
+        sr = audio.MODEL_RATE
+    return x, y, sr
+
+
 def evaluate(model, test_dir, target_dir, sampler_type="pc", predictor="reverse_diffusion", corrector="ald",
              corrector_steps=1, snr=0.5, N=30, reverse_starting_point=1.0, force_N=0, atol=1e-5, rtol=1e-5,
              timestep_type="linear", correct_stepsize=False, oracle=False, rank=0, world=1, batch_size=1,
-             max_frames=16384, **enhance_kw):
+             max_frames=16384, resample=False, **enhance_kw):
     """-> dict with 'filename' and METRICS lists (all files, every rank).  batch_size > 1: the rank's files run
     as ragged batches of at most batch_size rows and max_frames spectrogram frames (_evaluate_batched).
 
@@ -103,7 +122,7 @@ def evaluate(model, test_dir, target_dir, sampler_type="pc", predictor="reverse_
         batch_size = 1  # no batched enhancer for these settings (langevin, sebridge / sebridge_v2): the per-file loop
     if batch_size > 1:
         rows = _evaluate_batched(model, files, a, b, clean_dir, target_dir, pesq_fn, batch_size, max_frames,
-                                 clean_rms, noise_rms,
+                                 clean_rms, noise_rms, resample,
                                  dict(sampler_type=sampler_type, predictor=predictor, corrector=corrector,
                                       corrector_steps=corrector_steps, N=N, snr=snr, atol=atol, rtol=rtol,
                                       timestep_type=timestep_type, correct_stepsize=correct_stepsize, oracle=oracle,
@@ -111,8 +130,7 @@ def evaluate(model, test_dir, target_dir, sampler_type="pc", predictor="reverse_
         a = b  # the per-file loop below has nothing left
     for i in range(a, b):
         name = os.path.basename(files[i])
-        x, sr = audio.load(join(clean_dir, name))
-        y, _ = audio.load(files[i])
+        x, y, sr = load_pair(join(clean_dir, name), files[i], resample)
         x_hat = model.enhance(x, y, sampler_type=sampler_type, predictor=predictor, corrector=corrector,
                               corrector_steps=corrector_steps, N=N, snr=snr, atol=atol, rtol=rtol,
                               timestep_type=timestep_type, correct_stepsize=correct_stepsize, oracle=oracle,
@@ -146,7 +164,7 @@ def score_batch(x_hat, x, y, dev=None):
 
 
 def _evaluate_batched(model, files, a, b, clean_dir, target_dir, pesq_fn, batch_size, max_frames, clean_rms,
-                      noise_rms, kw):
+                      noise_rms, resample, kw):
     """Metric rows of files [a, b), enhanced as ragged batches: lengths from the WAV headers, the plan, then per
     batch one load, one enhance_batch call, the 16-bit files and one ragged energy_ratios launch with n = y - x
     formed on the device; PESQ on the host, file by file.  The seeds are drawn first, one per file in file order:
@@ -155,13 +173,16 @@ def _evaluate_batched(model, files, a, b, clean_dir, target_dir, pesq_fn, batch_
     idx = list(range(a, b))
     seeds = [int(torch.randint(0, 2 ** 62, (1,)).item()) for _ in idx]
     lens = [audio.info(files[i])[0] for i in idx]
+    if resample:  # the plan is made of the 16 kHz lengths, still from the headers alone
+        lens = [audio.resampled_length(L, audio.info(files[i])[2], audio.MODEL_RATE) for L, i in zip(lens, idx)]
     dev = torch.device("cuda", torch.cuda.current_device())
     rows = [None] * len(idx)
     oracle = kw["oracle"]
     for batch in plan_batches(lens, batch_size, max_frames):
         names = [os.path.basename(files[idx[k]]) for k in batch]
-        xs = [audio.load(join(clean_dir, nm)) for nm in names]
-        ys = [audio.load(files[idx[k]])[0] for k in batch]
+        pairs = [load_pair(join(clean_dir, nm), files[idx[k]], resample) for nm, k in zip(names, batch)]
+        xs = [(x, sr) for x, _, sr in pairs]
+        ys = [y for _, y, _ in pairs]
         x_hat = model.enhance_batch([y[0] for y in ys], seeds=[seeds[k] for k in batch], batch_size=len(batch),
                                     max_frames=max_frames,
                                     clean_rms=[clean_rms[idx[k]] for k in batch] if oracle else None,
@@ -198,11 +219,8 @@ def write_tables(data, target_dir):
         f.write(f"SI-SAR: {print_mean_std(data['si_sar'])} \n")
 
 
-def main(argv=None):
-    ap = argparse.ArgumentParser(description="eval.py on the MI355X path")
-    ap.add_argument("--destination_folder", type=str, required=True)
-    ap.add_argument("--test_dir", type=str, required=True)
-    ap.add_argument("--ckpt", type=str, required=True)
+def sampler_arguments(ap):
+    """The sampler options of eval.py (shared with snrse.enhance_files)."""
     ap.add_argument("--sampler_type", type=str, choices=("pc", "ode"), default="pc")
     ap.add_argument("--predictor", type=str, default="reverse_diffusion")
     ap.add_argument("--reverse_starting_point", type=float, default=1.0)
@@ -215,7 +233,25 @@ def main(argv=None):
     ap.add_argument("--rtol", type=float, default=1e-5)
     ap.add_argument("--timestep_type", type=str, default="linear")
     ap.add_argument("--correct_stepsize", action="store_true")
+
+
+def sampler_kwargs(a):
+    """evaluate()'s sampler keywords from the parsed sampler_arguments."""
+    return dict(sampler_type=a.sampler_type, predictor=a.predictor, corrector=a.corrector,
+                corrector_steps=a.corrector_steps, snr=a.snr, N=a.N, reverse_starting_point=a.reverse_starting_point,
+                force_N=a.force_N, atol=a.atol, rtol=a.rtol, timestep_type=a.timestep_type,
+                correct_stepsize=a.correct_stepsize)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description="eval.py on the MI355X path")
+    ap.add_argument("--destination_folder", type=str, required=True)
+    ap.add_argument("--test_dir", type=str, required=True)
+    ap.add_argument("--ckpt", type=str, required=True)
+    sampler_arguments(ap)
     ap.add_argument("--oracle", action="store_true")
+    ap.add_argument("--resample", action="store_true",
+                    help="bring clean / noisy files that are not at 16 kHz to 16 kHz on the device first")
     ap.add_argument("--batch_size", type=int, default=1,
                     help="files per ragged batch (1 = the per-file loop; files of one batch share their padded "
                          "frame count)")
@@ -225,11 +261,8 @@ def main(argv=None):
     model = ScoreModel.load_from_checkpoint(a.ckpt, base_dir="", batch_size=16, num_workers=0, kwargs=dict(gpu=False))
     model.eval(no_ema=False)
     model.cuda()
-    evaluate(model, a.test_dir, a.destination_folder, sampler_type=a.sampler_type, predictor=a.predictor,
-             corrector=a.corrector, corrector_steps=a.corrector_steps, snr=a.snr, N=a.N,
-             reverse_starting_point=a.reverse_starting_point, force_N=a.force_N, atol=a.atol, rtol=a.rtol,
-             timestep_type=a.timestep_type, correct_stepsize=a.correct_stepsize, oracle=a.oracle, rank=rank,
-             world=world, batch_size=a.batch_size)
+    evaluate(model, a.test_dir, a.destination_folder, **sampler_kwargs(a), oracle=a.oracle, rank=rank, world=world,
+             batch_size=a.batch_size, resample=a.resample)
 
 
 if __name__ == "__main__":

@@ -702,6 +702,71 @@ def absmax(sig, lengths=None):
     return out
 
 
+_RESAMPLE_TAPS = {}  # (up, down, device) -> (phase-major taps on the device, half): the default filter, built once
+
+
+def phase_major_taps(w, up):
+    """Filter w (float64 [2 half + 1], scipy's `window=` array) -> (h = up w phase-major [up, K] float32, half),
+    K = ceil((2 half + 1) / up), [p, j] = h[p + j up] and 0 past the filter: snrse_resample_poly's layout.
+    Computed in float64, rounded to float32 once."""
+    w = np.asarray(w, dtype=np.float64).reshape(-1)
+    if len(w) % 2 != 1:
+        raise ValueError(f"snrse: resample_poly takes an odd number of taps, got {len(w)}")
+    half = (len(w) - 1) // 2
+    K = (2 * half + up) // up
+    h = np.zeros(up * K, np.float64)
+    h[:len(w)] = up * w
+    return np.ascontiguousarray(h.reshape(K, up).T).astype(np.float32), half
+
+
+def resample_poly(x, up, down, lengths=None, taps=None):
+    """Rational polyphase FIR resampling of a ragged batch: x [B, stride_in] f32 on the device, row b valid on
+    [0, L_b) (lengths: a sequence / numpy / tensor, None = whole rows; L_b = 0 is allowed) -> (y [B, stride_out]
+    f32, out_lengths [B] int32), both on the device, n_out_b = ceil(L_b up / down), stride_out their maximum and
+    y zero from n_out_b on.  The arithmetic of scipy.signal.resample_poly(x, up, down, window=taps,
+    padtype='constant') in fp32; taps None is scipy's default filter (snrse.audio.resample_taps), cached on the
+    device per ratio.  up / down is reduced first; equal, the rows are copied.  One launch, no read-back (one for
+    lengths given as a device tensor)."""
+    _dev(x)
+    if x.dim() != 2 or x.dtype != torch.float32:
+        raise TypeError("snrse: resample_poly takes a [B, L] float32 batch")
+    B, Lin = x.shape
+    up, down = int(up), int(down)
+    if up <= 0 or down <= 0 or B <= 0:
+        raise ValueError(f"snrse: resample_poly needs rows and up, down > 0 (got {B} rows, {up} / {down})")
+    g = math.gcd(up, down)
+    up, down = up // g, down // g
+    if lengths is None:
+        host = np.full(B, Lin, np.int64)
+    else:
+        host = np.asarray(lengths.cpu() if torch.is_tensor(lengths) else lengths).astype(np.int64).reshape(-1)
+    if len(host) != B or (host < 0).any() or (host > Lin).any():
+        raise ValueError(f"snrse: resample_poly needs {B} lengths inside [0, {Lin}], the row stride of the batch")
+    out_host = -((-host * up) // down)
+    if out_host.max(initial=0) >= 2 ** 31:
+        raise ValueError("snrse: a resampled row would have 2^31 samples or more")
+    out_dev = torch.from_numpy(out_host.astype(np.int32)).to(x.device)
+    y = torch.empty(B, int(out_host.max()), device=x.device, dtype=torch.float32)
+    if y.shape[1] == 0:
+        return y, out_dev
+    ln_dev = torch.from_numpy(host.astype(np.int32)).to(x.device)
+    tp, half = None, 0
+    if (up, down) != (1, 1):
+        if taps is None:
+            key = (up, down, x.device)
+            if key not in _RESAMPLE_TAPS:
+                from .audio import resample_taps
+                pm, half = phase_major_taps(resample_taps(up, down), up)
+                _RESAMPLE_TAPS[key] = (torch.from_numpy(pm).to(x.device), half)
+            tp, half = _RESAMPLE_TAPS[key]
+        else:
+            pm, half = phase_major_taps(taps.cpu().numpy() if torch.is_tensor(taps) else taps, up)
+            tp = torch.from_numpy(pm).to(x.device)
+    _lib.call("snrse_resample_poly", _ptr(x) if Lin else None, ln_dev.data_ptr(), B, Lin, up, down, half, _ptr(tp),
+              y.data_ptr(), y.shape[1], _stream())
+    return y, out_dev
+
+
 def range_stats(t, peak=None, nonfinite=None, accumulate=False):
     """Range statistics of a contiguous device tensor whose leading dimension counts the rows (float32, float16,
     bfloat16, or complex64 read as interleaved floats): (peak [B] f32 = max |v| over the finite elements of each
