@@ -306,6 +306,34 @@ int snrse_resample_poly(const float* x, const int* lengths, int B, long long str
                         const float* taps, float* y, long long stride_out, hipStream_t stream);
 int snrse_resample_poly_block(void);
 
+/* ESTOI, the extended short-time objective intelligibility measure (Jensen & Taal 2016 with pystoi's conventions;
+ * csrc/estoi.hip), of a ragged batch: x clean and y processed, [B][stride] f32 at 10 kHz, lengths [B] int32 on the
+ * device (clamped to [0, stride]) -> out [B] f64 and info [B][2] int32 = (K, S).  For one row of length L, with the
+ * window w[n] = 0.5 (1 - cos(2 pi (n + 1) / 257)), n = 0..255, and eps = 2^-52:
+ *   1. frames i = 0..nf-1 start at 128 i for every i with 128 i < L - 256: nf = max(0, ceil((L - 256) / 128)), a
+ *      frame that would end exactly at L is not taken.  e_i = 20 log10(|w x[128 i : 128 i + 256]|_2 + eps); frame i is
+ *      kept iff e_i > max_i e_i - 40.  x alone decides, the same frames are kept in y: K frames f_0 < ... < f_{K-1}.
+ *   2. the kept frames are windowed and overlap-added at hop 128 into x' of 128 (K - 1) + 256 samples, and x' is framed
+ *      again by the rule of 1: M = K - 1 frames, X[:, j] = rfft(w x'[128 j : 128 j + 256], 512).  The same for y.
+ *   3. M < 30: out = 1e-5, S = 0.
+ *   4. 15 third-octave bands, centres 150 2^(k/3) Hz, edges the geometric means of neighbouring centres snapped to
+ *      the nearest bin: [7,9) [9,11) [11,14) [14,17) [17,22) [22,27) [27,34) [34,43) [43,55) [55,69) [69,87) [87,109)
+ *      [109,138) [138,174) [174,219).  Xb[k][j] = sqrt(sum over the bins of band k of |X[bin][j]|^2).
+ *   5. segments m = 0..S-1, S = M - 29: the 15 x 30 block Xb[:, m : m + 30] has each row's mean (over its 30 frames)
+ *      subtracted and is divided by (the row's L2 norm + eps), then each column's mean (over the 15 bands) subtracted
+ *      and divided by (the column's L2 norm + eps); the same for Yb; out = sum over m, k, j of the products / (30 S).
+ * The energies, the keep decision and step 5 are fp64; the spectra are fp32.  An all-zero row gives 0.0 with every
+ * frame kept.  Nothing at or past L of a row is read into a result.  No floating-point atomics: a row's bits are the
+ * same on every launch, launched alone, and under any permutation of the batch.  Five launches whatever B is, no
+ * host synchronisation.  work: work_bytes >= the workspace size of (B, stride) bytes of device memory, 256-byte
+ * aligned; snrse_estoi_workspace gives 0, no valid size, for B <= 0 or stride <= 0.  EINVAL, before any HIP call, for
+ * B <= 0, stride <= 0, a NULL pointer or a short workspace.
+ * snrse_estoi_block: re-framed frames per workgroup of the spectrum kernel (where the kernel changes block). */
+int snrse_estoi(const float* x, const float* y, const int* lengths, int B, long long stride, void* work,
+                size_t work_bytes, double* out, int* info, hipStream_t stream);
+size_t snrse_estoi_workspace(int B, long long stride);
+int snrse_estoi_block(void);
+
 /* Range statistics of a contiguous tensor [B][per] (dtype SNRSE_F32 / SNRSE_F16 / SNRSE_BF16; a complex64
  * spectrogram is 2*per floats): peak[b] = max |v| over the FINITE elements of row b (0 when there is none),
  * nonfinite[b] = number of inf / NaN elements of row b (saturating at INT_MAX).  accumulate == 0: overwrite

@@ -49,6 +49,7 @@ SIGNATURES = {
     "snrse_range_stats": [_vp, _i, _ll, _i, _vp, _vp, _i, _vp],
     "snrse_resample_poly": [_vp, _vp, _i, _ll, _i, _i, _i, _vp, _vp, _ll, _vp],
     "snrse_energy_ratios": [_vp, _vp, _vp, _i, _i, _vp, _vp],
+    "snrse_estoi": [_vp, _vp, _vp, _i, _ll, _vp, C.c_size_t, _vp, _vp, _vp],
     "snrse_input_conv": [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp],
     "snrse_input_conv_x3": [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "snrse_spec_transform": [_vp, _vp, C.c_longlong, _i, _vp],
@@ -97,6 +98,7 @@ HOUSEKEEPING = {"snrse_abi_version": ([], _i), "snrse_build_id": ([], C.c_char_p
                 "snrse_device_name": ([C.c_char_p, _i], _i), "snrse_snrnet_workspace": ([_i, _i], C.c_size_t),
                 "snrse_snrnet_train_workspace": ([_i, _i], C.c_size_t),
                 "snrse_rk45_rownorm_blocks": ([_i, _ll], _i), "snrse_resample_poly_block": ([], _i),
+                "snrse_estoi_workspace": ([_i, _ll], C.c_size_t), "snrse_estoi_block": ([], _i),
                 "snrse_ctx_create": ([], _vp), "snrse_ctx_destroy": ([_vp], None)}
 
 _lib = None

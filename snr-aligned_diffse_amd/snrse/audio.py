@@ -129,6 +129,23 @@ def resample_taps(up: int, down: int) -> np.ndarray:
     return w / w.sum()
 
 
+STOI_RATE = 10000  # the sample rate ESTOI is defined at
+
+
+def stoi_resample_taps(up: int, down: int) -> np.ndarray:
+    """The filter w ESTOI resamples with (pystoi's restatement of Octave's resample), float64 [2 Lh + 1], to be
+    applied as resample_poly(sig, up, down, window=w): cutoff fc = 1 / (2 max(up, down)), roll-off width fc / 10,
+    60 dB rejection, Lh = ceil((60 - 8) / (28.714 width)), a Kaiser window of beta 0.1102 (60 - 8.7) on
+    2 up fc sinc(2 fc t), t = -Lh..Lh, normalised to sum 1.  (5, 8), 16 kHz -> 10 kHz: 581 taps."""
+    rej = 60.0
+    fc = 1.0 / (2 * max(int(up), int(down)))
+    width = fc / 10.0
+    Lh = int(np.ceil((rej - 8.0) / (28.714 * width)))
+    t = np.arange(-Lh, Lh + 1, dtype=np.float64)
+    h = np.kaiser(2 * Lh + 1, 0.1102 * (rej - 8.7)) * (2 * int(up) * fc * np.sinc(2 * fc * t))
+    return h / h.sum()
+
+
 def write_wav(path: str, x: np.ndarray, sr: int = 16000, bits: int = 16):
     """Write [frames] or [frames, channels] float audio as PCM16 or float32 (test fixtures, outputs)."""
     x = np.asarray(x)

@@ -20,7 +20,9 @@ per-utterance arithmetic as the B=1 ScoreModel.enhance (model.py:702-839):
   * anything else (the sebridge / sebridge_v2 one-step branches) runs the per-variant
     ScoreModel.enhance loop.
 `si_sdr=True` adds si_sdr_<label> columns from snrse_energy_ratios (the reference keeps SI-SDR
-commented out in this script, deep_eval.py:146-148).
+commented out in this script, deep_eval.py:146-148).  `estoi=True` adds estoi_<label> columns and
+"ESTOI_<label>" lines: the nine variants of a file against its clean signal in one snrse.ops.estoi call (the device
+ESTOI built from the published definition; parity with pystoi unverified).
 
 Multi-GPU: files shard contiguously over ranks, rows meet with one all_gather.
 
@@ -115,8 +117,9 @@ def enhance_variants(model, ys, noise_rms, clean_rms=1.0, sampler_type="pc", pre
 def deep_evaluate(model, test_dir, target_dir, sampler_type="pc", predictor="reverse_diffusion", corrector="ald",
                   corrector_steps=1, snr=0.5, N=30, reverse_starting_point=1.0, force_N=0, atol=1e-5, rtol=1e-5,
                   timestep_type="linear", correct_stepsize=True, oracle=False, rank=0, world=1, batched=True,
-                  si_sdr=False, noise_tapes=None, verbose=True, resample=False):
-    """-> dict: 'filename' and 'pesq_<label>' (+ 'si_sdr_<label>') lists over all files (every rank).
+                  si_sdr=False, noise_tapes=None, verbose=True, resample=False, estoi=False):
+    """-> dict: 'filename' and 'pesq_<label>' (+ 'si_sdr_<label>', + 'estoi_<label>') lists over all files (every
+    rank).
     noise_tapes(file_index) -> noise_tape for that file's batch (parity runs).  resample: clean / noisy files that
     are not at 16 kHz are brought to it on the device as they are loaded (snrse.evaluate.load_pair); without it the
     rate is not looked at."""
@@ -133,7 +136,7 @@ def deep_evaluate(model, test_dir, target_dir, sampler_type="pc", predictor="rev
     files = sorted(glob("{}/*.wav".format(noisy_dir)))
     a, b = sdist.shard_range(len(files), rank, world)
     pesq_fn = _pesq_fn()
-    ncol = len(LABELS) * (2 if si_sdr else 1)
+    ncol = len(LABELS) * (1 + bool(si_sdr) + bool(estoi))
     rows = []
     run = [0.0] * len(LABELS)
     for cnt, i in enumerate(range(a, b)):
@@ -165,6 +168,12 @@ def deep_evaluate(model, test_dir, target_dir, sampler_type="pc", predictor="rev
             cl = torch.from_numpy(np.repeat(x[None, :Lm], len(LABELS), 0)).to(dev)
             nz = torch.from_numpy(np.ascontiguousarray(ys[:, :Lm] - x[None, :Lm])).to(dev)
             row += [float(v) for v in ops.energy_ratios(xs, cl, nz)[:, 0].cpu().numpy()]
+        if estoi:  # the nine variants against the one clean signal: one call
+            dev = torch.device("cuda", torch.cuda.current_device())
+            Lm = min(xh.shape[1], len(x))
+            xs = torch.from_numpy(np.ascontiguousarray(xh[:, :Lm], np.float32)).to(dev)
+            cl = torch.from_numpy(np.repeat(x[None, :Lm], len(LABELS), 0)).to(dev)
+            row += [float(v) for v in ops.estoi(cl, xs, fs=sr).cpu().numpy()]
         rows.append(row)
     dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
     allm = sdist.gather_metrics(rows if rows else np.zeros((0, ncol)), len(files), rank, world,
@@ -176,6 +185,9 @@ def deep_evaluate(model, test_dir, target_dir, sampler_type="pc", predictor="rev
     if si_sdr:
         for k, lab in enumerate(LABELS):
             data[f"si_sdr_{lab}"] = [float(v) for v in allm[:, len(LABELS) + k]]
+    if estoi:
+        for k, lab in enumerate(LABELS):
+            data[f"estoi_{lab}"] = [float(v) for v in allm[:, ncol - len(LABELS) + k]]
     if rank == 0:
         write_tables(data, target_dir)
     return data
@@ -191,6 +203,9 @@ def write_tables(data, target_dir):
     with open(join(target_dir, "_avg_results_deep.txt"), "w") as f:
         for lab in LABELS:
             f.write("PESQ_{0}: {1} \n".format(lab, print_mean_std(data[f"pesq_{lab}"], decimal=3)))
+        for lab in LABELS:
+            if f"estoi_{lab}" in data:
+                f.write("ESTOI_{0}: {1} \n".format(lab, print_mean_std(data[f"estoi_{lab}"], decimal=3)))
 
 
 def main(argv=None):
@@ -216,6 +231,8 @@ def main(argv=None):
     ap.add_argument("--oracle", action="store_true", help="SNR oracle (deep_eval.py's --oracle)")
     ap.add_argument("--per_variant", action="store_true", help="the reference's B=1 loop instead of one batch")
     ap.add_argument("--si_sdr", action="store_true")
+    ap.add_argument("--estoi", action="store_true",
+                    help="add estoi_<label> columns, computed on the device (parity with pystoi unverified)")
     ap.add_argument("--resample", action="store_true",
                     help="bring clean / noisy files that are not at 16 kHz to 16 kHz on the device first")
     ap.set_defaults(correct_stepsize=True)
@@ -229,7 +246,8 @@ def main(argv=None):
                   corrector=a.corrector, corrector_steps=a.corrector_steps, snr=a.snr, N=a.N,
                   reverse_starting_point=a.reverse_starting_point, force_N=a.force_N, atol=a.atol, rtol=a.rtol,
                   timestep_type=a.timestep_type, correct_stepsize=a.correct_stepsize, oracle=a.oracle,
-                  rank=rank, world=world, batched=not a.per_variant, si_sdr=a.si_sdr, resample=a.resample)
+                  rank=rank, world=world, batched=not a.per_variant, si_sdr=a.si_sdr, resample=a.resample,
+                  **(dict(estoi=True) if a.estoi else {}))
 
 
 if __name__ == "__main__":

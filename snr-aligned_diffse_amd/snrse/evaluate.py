@@ -8,6 +8,10 @@ SI-SDR / SI-SIR / SI-SAR (utils.py:10-35, the columns the reference keeps commen
 the batched device kernel snrse_energy_ratios with n = y - x.  Results go to _results.csv and
 _avg_results.txt ("mean ± std" over non-NaN values, utils.py:112-125).
 
+--estoi adds ESTOI (Jensen & Taal 2016 with pystoi's conventions) as a fifth metric, computed on the device by
+snrse.ops.estoi (csrc/estoi.hip) from the published definition: pystoi is not a dependency, parity with it is
+unverified, and without the flag neither the column nor the computation exists.
+
 Multi-GPU: files shard contiguously over ranks (snrse.dist.shard_range); the
 per-file metric rows meet on every rank with one all_gather (RCCL over xGMI on the GPU box,
 gloo in the CPU tests) and rank 0 writes the tables.
@@ -92,14 +96,20 @@ def load_pair(clean_path, noisy_path, resample=False):
 def evaluate(model, test_dir, target_dir, sampler_type="pc", predictor="reverse_diffusion", corrector="ald",
              corrector_steps=1, snr=0.5, N=30, reverse_starting_point=1.0, force_N=0, atol=1e-5, rtol=1e-5,
              timestep_type="linear", correct_stepsize=False, oracle=False, rank=0, world=1, batch_size=1,
-             max_frames=16384, resample=False, **enhance_kw):
+             max_frames=16384, resample=False, estoi=False, **enhance_kw):
     """-> dict with 'filename' and METRICS lists (all files, every rank).  batch_size > 1: the rank's files run
     as ragged batches of at most batch_size rows and max_frames spectrogram frames (_evaluate_batched).
 
     sampler_type="ode" with batch_size > 1 runs ScoreModel.enhance_batch's ODE route: every file integrates with
     its own adaptive step sizes and draws its prior from its own Philox seed, so the results do not depend on
     batch_size as long as it is > 1 -- but they are a different noise realisation from batch_size = 1, whose
-    per-file enhance() loop draws the prior from torch's device generator."""
+    per-file enhance() loop draws the prior from torch's device generator.
+
+    estoi=True: every row gains a fifth value, the device ESTOI of the enhanced file against the clean one
+    (estoi_batch -> snrse.ops.estoi; built from the published definition, parity with pystoi unverified), the
+    dict an 'estoi' list, _results.csv an estoi column after si_sar and _avg_results.txt an ESTOI line.  Off, the
+    default, nothing of it runs and the tables are the four-metric ones."""
+    metrics = METRICS + ("estoi",) if estoi else METRICS
     clean_dir, noisy_dir = join(test_dir, "clean"), join(test_dir, "noisy")
     os.makedirs(join(target_dir, "all"), exist_ok=True)
     if model.sde.__class__.__name__ == "OUVESDE":  # eval.py:105-108
@@ -126,7 +136,7 @@ def evaluate(model, test_dir, target_dir, sampler_type="pc", predictor="reverse_
                                  dict(sampler_type=sampler_type, predictor=predictor, corrector=corrector,
                                       corrector_steps=corrector_steps, N=N, snr=snr, atol=atol, rtol=rtol,
                                       timestep_type=timestep_type, correct_stepsize=correct_stepsize, oracle=oracle,
-                                      **enhance_kw))
+                                      **enhance_kw), **(dict(estoi=True) if estoi else {}))
         a = b  # the per-file loop below has nothing left
     for i in range(a, b):
         name = os.path.basename(files[i])
@@ -138,12 +148,15 @@ def evaluate(model, test_dir, target_dir, sampler_type="pc", predictor="reverse_
                               **enhance_kw)
         audio.write_wav(join(target_dir, "all", name), x_hat, 16000, bits=16)
         rows.append(score_files(np.asarray(x_hat, np.float32), x[0].numpy(), y[0].numpy(), sr, pesq_fn))
+        if estoi:
+            st = estoi_batch([np.asarray(x_hat, np.float32)], [x[0].numpy()], sr=sr)
+            rows[-1] = list(rows[-1]) + [float(st[0])]
     dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
-    allm = sdist.gather_metrics(rows if rows else np.zeros((0, len(METRICS))), len(files), rank, world,
+    allm = sdist.gather_metrics(rows if rows else np.zeros((0, len(metrics))), len(files), rank, world,
                                 dev if world > 1 and sdist_backend_is_nccl() else torch.device("cpu"))
-    allm = allm.reshape(len(files), len(METRICS)).cpu().numpy()
+    allm = allm.reshape(len(files), len(metrics)).cpu().numpy()
     data = {"filename": [os.path.basename(f) for f in files]}
-    for k, m in enumerate(METRICS):
+    for k, m in enumerate(metrics):
         data[m] = [float(v) for v in allm[:, k]]
     if rank == 0:
         write_tables(data, target_dir)
@@ -163,8 +176,21 @@ def score_batch(x_hat, x, y, dev=None):
     return ops.energy_ratios(sd[0], sd[1], sd[2] - sd[1], lengths=Ls).cpu().numpy(), Ls
 
 
+def estoi_batch(x_hat, x, dev=None, sr=16000):
+    """ESTOI of a batch of files of different lengths (lists of 1-D numpy float32: enhanced, clean) at `sr` Hz in
+    one ragged snrse.ops.estoi call: one [2, B, max L] upload, file b scored over its first
+    L_b = min(len x_hat, len x) samples as score_files crops them.  -> [B] numpy f64 (one read-back)."""
+    dev = dev or torch.device("cuda", torch.cuda.current_device())
+    Ls = [min(len(h), len(c)) for h, c in zip(x_hat, x)]
+    sig = np.zeros((2, len(Ls), max(Ls)), np.float32)
+    for r, (h, c) in enumerate(zip(x_hat, x)):
+        sig[0, r, :Ls[r]], sig[1, r, :Ls[r]] = c[:Ls[r]], h[:Ls[r]]
+    sd = torch.from_numpy(sig).to(dev)
+    return ops.estoi(sd[0], sd[1], lengths=Ls, fs=sr).cpu().numpy()
+
+
 def _evaluate_batched(model, files, a, b, clean_dir, target_dir, pesq_fn, batch_size, max_frames, clean_rms,
-                      noise_rms, resample, kw):
+                      noise_rms, resample, kw, estoi=False):
     """Metric rows of files [a, b), enhanced as ragged batches: lengths from the WAV headers, the plan, then per
     batch one load, one enhance_batch call, the 16-bit files and one ragged energy_ratios launch with n = y - x
     formed on the device; PESQ on the host, file by file.  The seeds are drawn first, one per file in file order:
@@ -198,6 +224,12 @@ def _evaluate_batched(model, files, a, b, clean_dir, target_dir, pesq_fn, batch_
                 except Exception:  # as score_files: NaN for any PESQ failure (eval.py:147-150)
                     p = float("nan")
             rows[k] = [p, float(er[r, 0]), float(er[r, 1]), float(er[r, 2])]
+        if estoi:  # files of one batch may differ in rate without --resample: one call per rate
+            for sr in sorted({s for _, s in xs}):
+                sel = [r for r in range(len(batch)) if xs[r][1] == sr]
+                st = estoi_batch([x_hat[r] for r in sel], [xs[r][0][0].numpy() for r in sel], dev, sr)
+                for r, v in zip(sel, st):
+                    rows[batch[r]].append(float(v))
     return rows
 
 
@@ -207,16 +239,20 @@ def sdist_backend_is_nccl():
 
 
 def write_tables(data, target_dir):
-    """_results.csv (one row per file) and _avg_results.txt (eval.py:159-170)."""
+    """_results.csv (one row per file) and _avg_results.txt (eval.py:159-170); with an 'estoi' list in data, the
+    estoi column after si_sar and the ESTOI line."""
+    metrics = METRICS + ("estoi",) if "estoi" in data else METRICS
     with open(join(target_dir, "_results.csv"), "w") as f:
-        f.write(",".join(["filename", *METRICS]) + "\n")
+        f.write(",".join(["filename", *metrics]) + "\n")
         for i, name in enumerate(data["filename"]):
-            f.write(",".join([name] + [repr(float(data[m][i])) for m in METRICS]) + "\n")
+            f.write(",".join([name] + [repr(float(data[m][i])) for m in metrics]) + "\n")
     with open(join(target_dir, "_avg_results.txt"), "w") as f:
         f.write(f"PESQ: {print_mean_std(data['pesq'])} \n")
         f.write(f"SI-SDR: {print_mean_std(data['si_sdr'])} \n")
         f.write(f"SI-SIR: {print_mean_std(data['si_sir'])} \n")
         f.write(f"SI-SAR: {print_mean_std(data['si_sar'])} \n")
+        if "estoi" in data:
+            f.write(f"ESTOI: {print_mean_std(data['estoi'])} \n")
 
 
 def sampler_arguments(ap):
@@ -255,6 +291,8 @@ def main(argv=None):
     ap.add_argument("--batch_size", type=int, default=1,
                     help="files per ragged batch (1 = the per-file loop; files of one batch share their padded "
                          "frame count)")
+    ap.add_argument("--estoi", action="store_true",
+                    help="add the ESTOI column, computed on the device (snrse.ops.estoi; pystoi parity unverified)")
     a = ap.parse_args(argv)
     rank, world, _ = sdist.init_from_env()
     from sgmse.model import ScoreModel
@@ -262,7 +300,7 @@ def main(argv=None):
     model.eval(no_ema=False)
     model.cuda()
     evaluate(model, a.test_dir, a.destination_folder, **sampler_kwargs(a), oracle=a.oracle, rank=rank, world=world,
-             batch_size=a.batch_size, resample=a.resample)
+             batch_size=a.batch_size, resample=a.resample, **(dict(estoi=True) if a.estoi else {}))
 
 
 if __name__ == "__main__":

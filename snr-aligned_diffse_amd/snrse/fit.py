@@ -155,7 +155,7 @@ def _val_groups(n, batch_size, limit):
     return groups[:_limit(len(groups), limit)]
 
 
-def validate(model, limit_val_batches=None, rank=0, world=1, seeder=None):
+def validate(model, limit_val_batches=None, rank=0, world=1, seeder=None, estoi=False):
     """One pass over the validation set with the EMA weights (Lightning puts the module in eval(), which the
     reference overrides to swap them in): valid_loss, the mean of validation_step over the clips; for a
     ScoreModel with num_eval_files != 0 also pesq / si_sdr / estoi (sgmse.util.inference.evaluate_model; not for
@@ -164,7 +164,8 @@ def validate(model, limit_val_batches=None, rank=0, world=1, seeder=None):
     world > 1: rank r takes the batches r, r + world, ...; the fp64 sums (loss x count, error x count, count) are
     all-reduced, so the values are the full set's means on every rank.  evaluate_model runs on rank 0 alone and
     its three numbers are broadcast.  seeder(j), when given, is called before validation batch j with
-    j = VAL_INDEX0 + batch number, and with EVAL_INDEX before evaluate_model (per-batch seeding)."""
+    j = VAL_INDEX0 + batch number, and with EVAL_INDEX before evaluate_model (per-batch seeding).  estoi: the
+    record's estoi is the device ESTOI of the chosen files (evaluate_model(estoi=True)) instead of NaN."""
     import torch
     from sgmse.snr_estimator import SNRModel
     dm = model.data_module
@@ -204,7 +205,8 @@ def validate(model, limit_val_batches=None, rank=0, world=1, seeder=None):
         if rank == 0:
             if seeder is not None:
                 seeder(EVAL_INDEX)
-            three = evaluate_model(model, model.num_eval_files)
+            three = evaluate_model(model, model.num_eval_files, estoi=True) if estoi else \
+                evaluate_model(model, model.num_eval_files)
         if world > 1:
             # one NFE per file: not worth sharding yet; the other ranks wait here for rank 0's numbers
             three = sdist.broadcast_floats(three, 3, device, src=0)
@@ -243,7 +245,7 @@ def _save_topk(ckpt_dir, last, monitor, mode, value, epoch, best):
 # ----------------------------------------------------------------------------- the loop
 def fit(model, max_epochs=None, max_steps=None, accumulate_grad_batches=1, gradient_clip_val=0.0,
         check_val_every_n_epoch=1, limit_train_batches=None, limit_val_batches=None, ckpt_dir=None, resume=None,
-        seed=0, log_path=None, rank=0, world=1, batch_seeding=False):
+        seed=0, log_path=None, rank=0, world=1, batch_seeding=False, estoi=False):
     """Train `model` (a ScoreModel of the built branches or an SNRModel) on its data module's train set.
     -> dict(epoch, global_step, epochs_run, optimizer, history (the validation records), log (every record)).
 
@@ -256,7 +258,8 @@ def fit(model, max_epochs=None, max_steps=None, accumulate_grad_batches=1, gradi
     parameters, moments and shadows (checked once per epoch, dist.check_replicas).  Validation is sharded,
     rank 0 writes the checkpoints and the log.  batch_seeding (always on for world > 1): every batch is seeded
     from (seed, epoch, its global index) -- seed_batch -- so a one-rank run with batch_seeding=True and
-    accumulation k W sees the batches, crops and draws of the W-rank run."""
+    accumulation k W sees the batches, crops and draws of the W-rank run.  estoi: the validation records carry
+    the device ESTOI (snrse.ops.estoi) of the evaluated files instead of null."""
     import torch
     from sgmse.ema import resume_checkpoint
     from sgmse.snr_estimator import SNRModel
@@ -350,7 +353,8 @@ def fit(model, max_epochs=None, max_steps=None, accumulate_grad_batches=1, gradi
             reducer.check_replicas()  # one fp64 checksum per rank, compared as bits
         if check_val_every_n_epoch and (epoch + 1) % check_val_every_n_epoch == 0:
             metrics = validate(model, limit_val_batches, rank, world,
-                               (lambda j, e=epoch: seed_batch(seed, e, j)) if per_batch else None)
+                               (lambda j, e=epoch: seed_batch(seed, e, j)) if per_batch else None,
+                               **(dict(estoi=True) if estoi else {}))
             rec = dict(step=global_step, epoch=epoch, **metrics)
             history.append(rec)
             log.validation(rec)
@@ -406,6 +410,9 @@ def build_parser(argv=None):
                     help="seed every batch from (seed, epoch, global batch index), as a run on several devices "
                          "always does: a one-device run then reproduces a multi-device one")
     base.add_argument("--gpus", type=int, default=1)
+    tr.add_argument("--estoi", action="store_true",
+                    help="score the validation files with ESTOI on the device (snrse.ops.estoi): the validation "
+                         "record's estoi is then a number instead of null")
     tr.add_argument("--seed", type=int, default=0)
     tr.add_argument("--log_path", type=str, default=None, help="default <ckpt_dir>/log.jsonl")
     temp, _ = base.parse_known_args(argv)
@@ -483,7 +490,8 @@ def _run(parser, temp, argv, rank, world):
               accumulate_grad_batches=args.accumulate_grad_batches, gradient_clip_val=args.gradient_clip_val,
               check_val_every_n_epoch=args.check_val_every_n_epoch, limit_train_batches=args.limit_train_batches,
               limit_val_batches=args.limit_val_batches, ckpt_dir=ckpt_dir, resume=args.resume_from_checkpoint,
-              seed=args.seed, log_path=log_path, rank=rank, world=world, batch_seeding=args.batch_seeding)
+              seed=args.seed, log_path=log_path, rank=rank, world=world, batch_seeding=args.batch_seeding,
+              **(dict(estoi=True) if args.estoi else {}))
     if rank == 0:
         print(json.dumps({"epoch": res["epoch"], "global_step": res["global_step"], "ckpt_dir": ckpt_dir,
                           "last": res["history"][-1] if res["history"] else None}))

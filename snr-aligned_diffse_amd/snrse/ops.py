@@ -725,7 +725,8 @@ def resample_poly(x, up, down, lengths=None, taps=None):
     f32, out_lengths [B] int32), both on the device, n_out_b = ceil(L_b up / down), stride_out their maximum and
     y zero from n_out_b on.  The arithmetic of scipy.signal.resample_poly(x, up, down, window=taps,
     padtype='constant') in fp32; taps None is scipy's default filter (snrse.audio.resample_taps), cached on the
-    device per ratio.  up / down is reduced first; equal, the rows are copied.  One launch, no read-back (one for
+    device per ratio; taps may also be a caller's cached (phase_major_taps on the device, half) pair, used as it
+    is.  up / down is reduced first; equal, the rows are copied.  One launch, no read-back (one for
     lengths given as a device tensor)."""
     _dev(x)
     if x.dim() != 2 or x.dtype != torch.float32:
@@ -759,12 +760,54 @@ def resample_poly(x, up, down, lengths=None, taps=None):
                 pm, half = phase_major_taps(resample_taps(up, down), up)
                 _RESAMPLE_TAPS[key] = (torch.from_numpy(pm).to(x.device), half)
             tp, half = _RESAMPLE_TAPS[key]
+        elif isinstance(taps, tuple):  # (phase-major taps on the device, half): a caller's own cache, used as it is
+            tp, half = taps
         else:
             pm, half = phase_major_taps(taps.cpu().numpy() if torch.is_tensor(taps) else taps, up)
             tp = torch.from_numpy(pm).to(x.device)
     _lib.call("snrse_resample_poly", _ptr(x) if Lin else None, ln_dev.data_ptr(), B, Lin, up, down, half, _ptr(tp),
               y.data_ptr(), y.shape[1], _stream())
     return y, out_dev
+
+
+_STOI_TAPS = {}  # (up, down, device) -> ESTOI's resampling filter (snrse.audio.stoi_resample_taps) on the device
+
+
+def estoi(x, y, lengths=None, fs=16000, return_info=False):
+    """ESTOI (Jensen & Taal 2016 with pystoi's conventions; the definition stands at snrse_estoi in
+    include/snrse.h) of a ragged batch: x clean, y processed, [B, L] f32 on the device at `fs` Hz, row b valid on
+    [0, L_b) (lengths None = whole rows) -> [B] f64 on the device.  fs != 10000: both signals are first resampled
+    to 10 kHz by resample_poly with ESTOI's own filter (cached on the device per ratio), then one snrse_estoi call.
+    Rows with fewer than 30 frames after the silent-frame removal give 1e-5.  return_info: also the [B, 2] int32
+    tensor (K kept frames, S segments; S = 0 marks the 1e-5 rows).  No read-back."""
+    if x.dim() != 2 or x.shape != y.shape or x.dtype != torch.float32 or y.dtype != torch.float32:
+        raise TypeError("snrse: estoi takes two [B, L] float32 batches of one shape")
+    B, L = x.shape
+    if B <= 0 or L <= 0:
+        raise ValueError(f"snrse: estoi needs a non-empty batch, got [{B}, {L}]")
+    x, y = x.contiguous(), y.contiguous()
+    _dev(x, y)
+    if lengths is None:
+        lengths = np.full(B, L, np.int64)
+    ln = as_lengths(lengths, B, L, x.device)
+    ln_dev = ln.dev
+    from .audio import STOI_RATE, rational, stoi_resample_taps
+    up, down = rational(int(fs), STOI_RATE)
+    if (up, down) != (1, 1):
+        key = (up, down, x.device)
+        if key not in _STOI_TAPS:
+            pm, half = phase_major_taps(stoi_resample_taps(up, down), up)
+            _STOI_TAPS[key] = (torch.from_numpy(pm).to(x.device), half)
+        x, ln_dev = resample_poly(x, up, down, lengths=ln.host, taps=_STOI_TAPS[key])
+        y, _ = resample_poly(y, up, down, lengths=ln.host, taps=_STOI_TAPS[key])
+        L = x.shape[1]
+    nbytes = int(_lib.load().snrse_estoi_workspace(B, L))
+    work = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
+    out = torch.empty(B, device=x.device, dtype=torch.float64)
+    info = torch.empty(B, 2, device=x.device, dtype=torch.int32)
+    _lib.call("snrse_estoi", x.data_ptr(), y.data_ptr(), ln_dev.data_ptr(), B, L, work.data_ptr(), nbytes,
+              out.data_ptr(), info.data_ptr(), _stream())
+    return (out, info) if return_info else out
 
 
 def range_stats(t, peak=None, nonfinite=None, accumulate=False):
