@@ -13,6 +13,7 @@ import torch
 import torch.nn as nn
 
 from snrse import ncsnpp as _hip
+from snrse import ops
 
 from .shared import BackboneRegistry
 
@@ -124,7 +125,7 @@ class NCSNpp(nn.Module):
             dt = {"bf16": torch.bfloat16, torch.bfloat16: torch.bfloat16, "fp16": torch.float16,
                   torch.float16: torch.float16}.get(self.compute_dtype, torch.float32)
             gemm = "x3" if self.compute_dtype == "fp32x3" else "exact"  # split-bf16 fp32 GEMMs
-            dev = device or (torch.device("cuda", torch.cuda.current_device()))
+            dev = device or ops.current_device()
             for k in [k for k, (pk, _) in self._hip_nets.items() if pk[1:] != key[1:]]:
                 del self._hip_nets[k]  # executors of parameters that are gone
             held = self._hip_nets[self.compute_dtype] = (

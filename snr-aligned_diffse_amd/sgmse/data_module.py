@@ -32,7 +32,7 @@ def get_window(window_type, window_length):
 def _device():
     if not torch.cuda.is_available():
         raise RuntimeError("Specs: the front-end runs on the HIP device (no CPU fallback)")
-    return torch.device("cuda", torch.cuda.current_device())
+    return ops.current_device()
 
 
 class Specs(torch.utils.data.Dataset):

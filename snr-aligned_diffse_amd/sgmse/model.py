@@ -30,6 +30,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from snrse import enhance as _enh
 from snrse import guard as _guard
 from snrse import ops
 from snrse import sampler as _samp
@@ -42,8 +43,7 @@ from .ema import save_checkpoint as _save_checkpoint
 from .sdes import SDERegistry
 from .util.other import pad_spec, pad_spec_16, snr_dB  # noqa: F401  (re-exported like the reference)
 
-i_30 = np.arange(1, 30 + 1)
-t_30 = (0.001 ** (1 / 7) + (i_30 - 1) / (30 - 1) * (1 ** (1 / 7) - 0.001 ** (1 / 7))) ** 7
+t_30 = _enh.T_30  # the reference's module-level time grid (model.py:22-23) under its name
 
 # what ScoreModel._step and the training entry point (snrse.fit) say for the branches that are not built
 TRAIN_UNSUPPORTED = ("the HIP training step is built for model_type='sebridge_v3' with "
@@ -70,10 +70,6 @@ def get_snr_model():
 def set_snr_model(model):
     global _snr_model
     _snr_model = model
-
-
-def _noise_seed():
-    return int(torch.randint(0, 2 ** 62, (1,)).item())
 
 
 class ScoreModel(nn.Module):
@@ -159,16 +155,7 @@ class ScoreModel(nn.Module):
 
     def fused_score_step(self, Yc):
         """Step function for the PC loop: NCSN++ pyramid + output head + SDE update in one kernel."""
-        net = self.dnn.hip(Yc.device)
-        mode = self._score_mode()
-
-        def step(x, tv, coef, z, seed, off):
-            pyr = net.pyramid(x, Yc, tv)
-            xo, xm, _ = ops.score_update(pyr, net.W["out_w"], net.W["out_b"], tv, mode, x, Yc, coef=coef, noise=z,
-                                         offset=off, **_samp.row_seed_kw(seed))
-            return xo, xm
-
-        return step
+        return _enh.fused_step(self.dnn.hip(Yc.device), Yc, self._score_mode())
 
     # ------------------------------------------------------------------ training (SURVEY.md §8(f) 2)
     def configure_optimizers(self):
@@ -195,7 +182,7 @@ class ScoreModel(nn.Module):
         self.data_module._check()
         x, y = batch[0], batch[1]
         B = x.shape[0]
-        dev = torch.device("cuda", torch.cuda.current_device())
+        dev = ops.current_device()
         X = x.to(dev, torch.complex64).reshape(B, x.shape[-2], x.shape[-1]).contiguous()
         Y = y.to(dev, torch.complex64).reshape(B, y.shape[-2], y.shape[-1]).contiguous()
         if n is None:
@@ -203,7 +190,7 @@ class ScoreModel(nn.Module):
         n = np.asarray(n.cpu() if torch.is_tensor(n) else n).reshape(B)
         if noise is None:
             coef = torch.tensor([[0.0, 0.0, 0.0, 1.0]] * B, device=dev)
-            z = ops.axpby_noise(coef, like=X, seed=_noise_seed())
+            z = ops.axpby_noise(coef, like=X, seed=_samp.draw_seed())
         else:
             z = noise.to(dev, torch.complex64).reshape(X.shape).contiguous()
         return _train.consistency_loss(self.dnn, X, Y, n, z, float(self.sigma_max), self.loss_type,
@@ -316,17 +303,55 @@ class ScoreModel(nn.Module):
         if self.snr_conditioned not in ("true", "false"):
             # the reference falls through every branch and fails on the unbound `sample` (model.py:826)
             raise NotImplementedError(f"snr_conditioned={self.snr_conditioned!r} has no enhance branch")
-        dev = torch.device("cuda", torch.cuda.current_device())
+        dev = ops.current_device()
         T_orig = y.size(1)
         yd = y.to(dev, torch.float32).reshape(1, -1).contiguous()
-        nf = ops.absmax(yd)  # norm_factor = max|y| (model.py:726)
-        Tp = T_orig // 128 + 1
-        Tp = Tp + (64 - Tp % 64) % 64
+        nf = ops.absmax(yd)  # norm_factor = max|y| (model.py:726), taken once: a fallback run divides by the same
         noise_tape = kwargs.get("noise_tape")
 
         def run():
-            return self._enhance_spec(yd, nf, T_orig, Tp, mode, dev, noise_tape, sampler_type, predictor, corrector, N,
-                                      corrector_steps, snr, oracle, clean_rms, noise_rms, kwargs)
+            """The network part: normalised utterance -> (enhanced spectrogram [1, F, Tp], nfe, iSTFT scale), in
+            the backbone's current compute_dtype."""
+            nfe, div = 1, nf
+            if self.snr_conditioned == "true":
+                if self.model_type != "sebridge_v3":
+                    raise NotImplementedError("snr_conditioned='true' is implemented for model_type='sebridge_v3' "
+                                              "(the sebridge_v2 branch needs the 3-argument NCSNpp_snr)")
+                if oracle:
+                    est_snr = float(noise_rms) / float(clean_rms)  # model.py:722-724
+                else:  # y / max|y|, raw STFT, pad_spec_16
+                    raw = ops.stft(yd, 1.0, tpad=_enh.pad_frames(1 + T_orig // 128, 16), mode=0, in_div=nf)
+                    est_snr = float(get_snr_model().estimate_from_spec(raw)[0])
+                # calculate_snr_direct snapped to t_30, calculate_normfac_direct there (model.py:734-736, 810-817)
+                t_hat = float(_enh.snap_t(est_snr, self.fixed_snr)[0])
+                div = nf * float(_enh.normfac(t_hat, self.fixed_snr))
+                Y = _enh.front_end(yd, mode, div=div)[0]
+                Z = noise_tape(0) if noise_tape is not None else None
+                coef = torch.tensor([[0.0, 1.0, 0.0, float(self.sigma_max) * t_hat]], device=dev)
+                X_T = ops.axpby_noise(coef, y=Y, noise=Z, seed=_samp.draw_seed())
+                sample = self(X_T[:, None], torch.full((1, 1, 1, 1), t_hat, device=dev), Y[:, None])[:, 0]
+                return sample, nfe, div
+            Y = _enh.front_end(yd, mode, div=div)[0]
+            if self.model_type == "bbed":
+                if sampler_type == "pc":
+                    sampler = self.get_pc_sampler(predictor, corrector, Y[:, None], N=N,
+                                                  corrector_steps=corrector_steps, snr=snr, noise_tape=noise_tape)
+                elif sampler_type == "ode":
+                    sampler = self.get_ode_sampler(Y[:, None], N=N, **kwargs)
+                else:
+                    raise ValueError(f"{sampler_type} is not a valid sampler type!")
+                sample, nfe = sampler()
+                sample = sample[:, 0]
+            elif self.model_type in ("sebridge", "sebridge_v2"):
+                t = 0.999
+                zs = 0.0 if self.model_type == "sebridge" else float(self.sigma_max) * t
+                Z = noise_tape(0) if (noise_tape is not None and zs) else None
+                X_T = ops.axpby_noise(torch.tensor([[0.0, 1.0, 0.0, zs]], device=dev), y=Y, noise=Z,
+                                      seed=_samp.draw_seed())
+                sample = self(X_T[:, None], torch.full((1, 1, 1, 1), t, device=dev), Y[:, None])[:, 0]
+            else:
+                raise NotImplementedError(f"model_type={self.model_type!r} with snr_conditioned='false'")
+            return sample, nfe, div
 
         fmt = self.dnn.compute_dtype
         policy = _guard.resolve(range_guard, torch.float16 if fmt in ("fp16", torch.float16) else None)
@@ -344,8 +369,7 @@ class ScoreModel(nn.Module):
                 torch.cuda.set_rng_state(rng[1], dev)
                 with self._compute_format(self.RANGE_FALLBACK):
                     sample, nfe, out_scale = run()
-        x_hat = ops.istft(sample.contiguous(), T_orig, mode=mode, out_scale=out_scale.reshape(1).contiguous())
-        x_hat = x_hat[0].cpu().numpy()
+        x_hat = _enh.back_end(sample, T_orig, mode, out_scale.reshape(1))[0].cpu().numpy()
         if timeit:
             rtf = (time.time() - start) / (len(x_hat) / 16000)
             return x_hat, nfe, rtf
@@ -363,6 +387,22 @@ class ScoreModel(nn.Module):
         if self.snr_conditioned == "false" and self.model_type == "bbed" and sampler_type == "ode":
             return "ode"  # the corrector plays no part in the probability-flow ODE
         return None  # the batch-mean `langevin` corrector, sebridge / sebridge_v2
+
+    def batched_enhancer(self, route, net, range_guard="auto", predictor="reverse_diffusion", corrector="ald", N=30,
+                         corrector_steps=1, snr=0.5, oracle=False, rtol=1e-5, atol=1e-5):
+        """The snrse.enhance enhancer of a _batch_route `route` on the executor `net` (self.dnn.hip(dev)), set up
+        from this model's SDE, t_eps, fixed_snr, sigma_max and data-module transform."""
+        common = dict(transform="exponent" if self.data_module.hip_mode() == 1 else "none", guard=range_guard)
+        if route == "pc":
+            return _enh.PCEnhancer(net, self.sde.copy().spec(), N=N, eps=self.t_eps, snr=snr, predictor=predictor,
+                                   corrector=corrector, corrector_steps=corrector_steps,
+                                   score_mode=self._score_mode(), **common)
+        if route == "ode":
+            return _enh.ODEEnhancer(net, self.sde.copy().spec(), eps=self.t_eps, rtol=rtol, atol=atol,
+                                    score_mode=self._score_mode(), **common)
+        snr_fn = None if oracle else (lambda raw: get_snr_model().estimate_from_spec(raw))
+        return _enh.SNRAlignedEnhancer(net, snr_fn=snr_fn, fixed_snr=float(self.fixed_snr),
+                                       sigma_max=float(self.sigma_max), **common)
 
     @torch.no_grad()
     def enhance_batch(self, ys, seeds=None, batch_size=32, max_frames=16384, sampler_type="pc",
@@ -396,7 +436,6 @@ class ScoreModel(nn.Module):
         are drawn as without it, before any device work.  output_rate "model" returns the 16 kHz waveforms,
         "input" resamples each back to its own rate and cuts it to exactly L_i samples."""
         from snrse import batching
-        from snrse.enhance import ODEEnhancer, PCEnhancer, SNRAlignedEnhancer
         n = len(ys)
         route = self._batch_route(sampler_type, corrector, kwargs)
         if sample_rates is not None:
@@ -406,7 +445,7 @@ class ScoreModel(nn.Module):
             if len(sample_rates) != n:
                 raise ValueError(f"enhance_batch: {len(sample_rates)} sample rates for {n} utterances")
             if seeds is None and route is not None:
-                seeds = [_noise_seed() for _ in range(n)]
+                seeds = [_samp.draw_seed() for _ in range(n)]
             lens_in = [int(resample.as_signal(y).numel()) for y in ys]
             # the batched enhancers gather their ragged batches on the device, where the resampled rows already are
             ys16 = resample.convert(ys, sample_rates, audio.MODEL_RATE, on_device=route is not None)
@@ -428,44 +467,28 @@ class ScoreModel(nn.Module):
                                         noise_rms=noise_rms[i] if oracle else 1, range_guard=range_guard, **kwargs))
             return out
         if seeds is None:
-            seeds = [_noise_seed() for _ in range(n)]
+            seeds = [_samp.draw_seed() for _ in range(n)]
         if len(seeds) != n:
             raise ValueError(f"enhance_batch: {len(seeds)} seeds for {n} utterances")
         if oracle and (clean_rms is None or noise_rms is None or len(clean_rms) != n or len(noise_rms) != n):
             raise ValueError("enhance_batch(oracle=True) takes clean_rms and noise_rms, one value per utterance")
-        mode = self.data_module.hip_mode()
+        self.data_module.hip_mode()  # a configuration the kernels are not built for fails before any device work
         sigs = [torch.as_tensor(np.asarray(y) if not torch.is_tensor(y) else y).to(torch.float32).reshape(-1)
                 for y in ys]
         lens = [int(s.numel()) for s in sigs]
         plan = batching.plan_batches(lens, batch_size, max_frames)
-        dev = torch.device("cuda", torch.cuda.current_device())
+        dev = ops.current_device()
         out = [None] * n
         with self._compute_format(self.RANGE_FALLBACK if self._range_fallback else self.dnn.compute_dtype):
-            net = self.dnn.hip(dev)
-            transform = "exponent" if mode == 1 else "none"
-            if route == "pc":
-                sde = self.sde.copy()
-                enh = PCEnhancer(net, sde.spec(), N=N, eps=self.t_eps, snr=snr, predictor=predictor,
-                                 corrector=corrector, corrector_steps=corrector_steps, score_mode=self._score_mode(),
-                                 transform=transform, guard=range_guard)
-            elif route == "ode":
-                enh = ODEEnhancer(net, self.sde.copy().spec(), eps=self.t_eps, rtol=kwargs.get("rtol", 1e-5),
-                                  atol=kwargs.get("atol", 1e-5), score_mode=self._score_mode(), transform=transform,
-                                  guard=range_guard)
-            else:
-                snr_fn = None if oracle else (lambda raw: get_snr_model().estimate_from_spec(raw))
-                enh = SNRAlignedEnhancer(net, snr_fn=snr_fn, fixed_snr=float(self.fixed_snr),
-                                         sigma_max=float(self.sigma_max), transform=transform, guard=range_guard)
+            enh = self.batched_enhancer(route, self.dnn.hip(dev), range_guard, predictor, corrector, N,
+                                        corrector_steps, snr, oracle, kwargs.get("rtol", 1e-5),
+                                        kwargs.get("atol", 1e-5))
             flagged = []
             ode_stats = self.last_ode_stats = []
             for rows in plan:
-                stride = max(lens[i] for i in rows)
-                on_dev = sigs[rows[0]].is_cuda  # rows resampled on the device (sample_rates): all of them are there
-                buf = torch.zeros(len(rows), stride, dtype=torch.float32, device=dev if on_dev else None)
-                for r, i in enumerate(rows):
-                    buf[r, :lens[i]] = sigs[i]
+                # rows resampled on the device (sample_rates) are packed there: all of a call's rows are, or none
+                buf, ln = batching.pack_rows([sigs[i] for i in rows])
                 yb = buf.to(dev)
-                ln = [lens[i] for i in rows]
                 rs = torch.tensor([seeds[i] for i in rows], dtype=torch.int64, device=dev)
                 if route in ("pc", "ode"):
                     xb, nfe = enh(yb, noise=_samp.NoiseSource(row_seeds=rs), lengths=ln)
@@ -494,57 +517,6 @@ class ScoreModel(nn.Module):
             yield
         finally:
             self.dnn.compute_dtype = prev
-
-    def _enhance_spec(self, yd, nf, T_orig, Tp, mode, dev, noise_tape, sampler_type, predictor, corrector, N,
-                      corrector_steps, snr, oracle, clean_rms, noise_rms, kwargs):
-        """The network part of enhance(): normalised utterance -> (enhanced spectrogram [1, F, Tp], nfe, iSTFT
-        scale), in the backbone's current compute_dtype."""
-        nfe = 1
-        if self.snr_conditioned == "true":
-            if self.model_type != "sebridge_v3":
-                raise NotImplementedError("snr_conditioned='true' is implemented for model_type='sebridge_v3' "
-                                          "(the sebridge_v2 branch needs the 3-argument NCSNpp_snr)")
-            if oracle:
-                est_snr = float(noise_rms) / float(clean_rms)  # model.py:722-724
-            else:
-                T16 = T_orig // 128 + 1
-                T16 = T16 + (16 - T16 % 16) % 16
-                raw = ops.stft(yd, 1.0, tpad=T16, mode=0, in_div=nf)  # y / max|y|, raw STFT, pad_spec_16
-                est_snr = float(get_snr_model().estimate_from_spec(raw)[0])
-            t_hat = float(t_30[np.abs(t_30 - est_snr / (10 ** 0.25 * self.fixed_snr)).argmin()])
-            normfac = self.calculate_normfac_direct(1.0, 10 ** 0.25 * self.fixed_snr * t_hat, self.fixed_snr)
-            div = nf * float(normfac)
-            Y = ops.stft(yd, 1.0, tpad=Tp, mode=mode, in_div=div)
-            z_scale = float(self.sigma_max) * t_hat
-            Z = noise_tape(0) if noise_tape is not None else None
-            coef = torch.tensor([[0.0, 1.0, 0.0, z_scale]], device=dev)
-            X_T = ops.axpby_noise(coef, y=Y, noise=Z, seed=_noise_seed())
-            sample = self(X_T[:, None], torch.full((1, 1, 1, 1), t_hat, device=dev), Y[:, None])[:, 0]
-            out_scale = div
-        else:
-            div = nf
-            Y = ops.stft(yd, 1.0, tpad=Tp, mode=mode, in_div=div)
-            if self.model_type == "bbed":
-                if sampler_type == "pc":
-                    sampler = self.get_pc_sampler(predictor, corrector, Y[:, None], N=N, corrector_steps=corrector_steps,
-                                                  snr=snr, noise_tape=noise_tape)
-                elif sampler_type == "ode":
-                    sampler = self.get_ode_sampler(Y[:, None], N=N, **kwargs)
-                else:
-                    raise ValueError(f"{sampler_type} is not a valid sampler type!")
-                sample, nfe = sampler()
-                sample = sample[:, 0]
-            elif self.model_type in ("sebridge", "sebridge_v2"):
-                t = 0.999
-                zs = 0.0 if self.model_type == "sebridge" else float(self.sigma_max) * t
-                Z = noise_tape(0) if (noise_tape is not None and zs) else None
-                X_T = ops.axpby_noise(torch.tensor([[0.0, 1.0, 0.0, zs]], device=dev), y=Y, noise=Z,
-                                      seed=_noise_seed())
-                sample = self(X_T[:, None], torch.full((1, 1, 1, 1), t, device=dev), Y[:, None])[:, 0]
-            else:
-                raise NotImplementedError(f"model_type={self.model_type!r} with snr_conditioned='false'")
-            out_scale = div
-        return sample, nfe, out_scale
 
 
 __all__ = ["ScoreModel", "t_30", "get_snr_model", "set_snr_model", "warnings"]

@@ -40,7 +40,7 @@ def get_pc_sampler(predictor_name, corrector_name, sde, score_fn, Y, Y_prior=Non
             B = Y.shape[0]
             Yc = Y.to(torch.complex64).reshape(B, Y.shape[-2], Y.shape[-1]).contiguous()
             Yp = None if Y_prior is None else Y_prior.to(torch.complex64).reshape(Yc.shape).contiguous()
-            sd = seed if seed is not None else int(torch.randint(0, 2 ** 62, (1,)).item())
+            sd = seed if seed is not None else _s.draw_seed()
             src = _s.NoiseSource(seed=sd, tape=noise_tape)
             fused = getattr(score_fn, "fused_score_step", None)
             if fused is not None:

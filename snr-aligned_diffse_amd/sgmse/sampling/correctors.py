@@ -5,9 +5,9 @@ import math
 import torch
 
 from snrse import ops
+from snrse.sampler import draw_seed
 
 from ..util.registry import Registry
-from .predictors import _noise_seed
 
 CorrectorRegistry = Registry("Corrector")
 
@@ -38,7 +38,7 @@ class LangevinCorrector(Corrector):
         for _ in range(self.n_steps):
             grad = self.score_fn(x, t, *args)
             unit = torch.tensor([[0.0, 0.0, 0.0, 1.0]] * B, device=x.device)
-            z = ops.axpby_noise(unit, like=_flat(x), seed=_noise_seed())
+            z = ops.axpby_noise(unit, like=_flat(x), seed=draw_seed())
             gn = torch.linalg.vector_norm(grad.reshape(B, -1), dim=-1).mean()
             nn_ = torch.linalg.vector_norm(z.reshape(B, -1), dim=-1).mean()
             e = (self.snr * nn_ / gn) ** 2 * 2
@@ -64,7 +64,7 @@ class AnnealedLangevinDynamics(Corrector):
         x_mean = x
         for _ in range(self.n_steps):
             grad = self.score_fn(x, t, y)
-            xo, xm = ops.sde_update(_flat(x), coef, score=_flat(grad), seed=_noise_seed())
+            xo, xm = ops.sde_update(_flat(x), coef, score=_flat(grad), seed=draw_seed())
             x, x_mean = xo.reshape(x.shape), xm.reshape(x.shape)
         return x, x_mean
 

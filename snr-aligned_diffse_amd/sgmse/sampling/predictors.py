@@ -5,14 +5,11 @@ import math
 import torch
 
 from snrse import ops
+from snrse.sampler import draw_seed
 
 from ..util.registry import Registry
 
 PredictorRegistry = Registry("Predictor")
-
-
-def _noise_seed():
-    return int(torch.randint(0, 2 ** 62, (1,)).item())
 
 
 class Predictor(abc.ABC):
@@ -38,7 +35,7 @@ class Predictor(abc.ABC):
         xv = x.reshape(B, x.shape[-2], x.shape[-1]).contiguous()
         yv = None if y is None else y.reshape(xv.shape).contiguous()
         sv = score.reshape(xv.shape).contiguous()
-        xo, xm = ops.sde_update(xv, coef, y=yv, score=sv, seed=_noise_seed())
+        xo, xm = ops.sde_update(xv, coef, y=yv, score=sv, seed=draw_seed())
         return xo.reshape(x.shape), xm.reshape(x.shape)
 
 

@@ -31,7 +31,7 @@ def evaluate_model(model, num_eval_files, batch_size=8, seeds=None, estoi=False,
     estoi=True: the third value is the mean device ESTOI of the files (snrse.evaluate.estoi_batch, one ragged
     snrse.ops.estoi call; its parity with pystoi is unverified, the package being absent); False: NaN."""
     from snrse import audio
-    from snrse.evaluate import _pesq_fn, score_batch
+    from snrse.evaluate import _pesq_fn, pesq_or_nan, score_batch
     dm = model.data_module
     vs = dm.valid_set_2 if model.snr_conditioned == "fixed" else dm.valid_set
     idx = eval_indices(len(vs.clean_files), num_eval_files)
@@ -47,15 +47,7 @@ def evaluate_model(model, num_eval_files, batch_size=8, seeds=None, estoi=False,
     er, Ls = score_batch([np.asarray(h, np.float32) for h in x_hat], [x[0].numpy() for x, _ in xs],
                          [y[0].numpy() for y in ys])
     pesq_fn = _pesq_fn()
-    pesq = []
-    for (x, sr), h, L in zip(xs, x_hat, Ls):
-        p = float("nan")
-        if pesq_fn is not None:
-            try:
-                p = float(pesq_fn(sr, x[0, :L].numpy(), np.asarray(h[:L]), "wb"))
-            except Exception:  # as snrse.evaluate: NaN for any PESQ failure
-                p = float("nan")
-        pesq.append(p)
+    pesq = [pesq_or_nan(pesq_fn, sr, x[0, :L].numpy(), np.asarray(h[:L])) for (x, sr), h, L in zip(xs, x_hat, Ls)]
     st = float("nan")
     if estoi:
         from snrse.evaluate import estoi_batch

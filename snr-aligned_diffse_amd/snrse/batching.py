@@ -1,4 +1,4 @@
-"""Batch planner for utterances of different lengths (pure host code).
+"""Batch planner and row packer for utterances of different lengths (host code: no call into the library).
 
 Utterances whose spectrograms pad to the same frame count Tpad = pad_frames(1 + L // 128, 64) have identical
 network shapes, and no kernel of the enhancement path mixes batch rows, so they can share one
@@ -8,9 +8,23 @@ larger bucket, which would change their results.
 """
 from __future__ import annotations
 
+import torch
+
 from .enhance import pad_frames
 
 MIN_LENGTH = 256  # a shorter clip cannot be reflect-padded by n_fft // 2 = 255 samples (torch.stft refuses it too)
+
+
+def pack_rows(sigs):
+    """1-D signals of different lengths (numpy arrays or tensors, all on one device) -> (buf [B, max(max L, 1)]
+    float32 where the signals are, row b holding signal b and zeros after it, [L_b]).  An empty signal is a row
+    of zeros with L_b = 0."""
+    rows = [torch.as_tensor(s).reshape(-1) for s in sigs]
+    lens = [int(r.numel()) for r in rows]
+    buf = torch.zeros(len(rows), max(max(lens), 1), dtype=torch.float32, device=rows[0].device)
+    for b, r in enumerate(rows):
+        buf[b, :lens[b]] = r
+    return buf, lens
 
 
 def frames(length):

@@ -38,8 +38,11 @@ from os.path import join
 import numpy as np
 import torch
 
-from . import audio, dist as sdist, ops
-from .evaluate import _pesq_fn, load_pair, print_mean_std, sdist_backend_is_nccl
+from . import audio, dist as sdist, enhance, ops
+from .batching import pack_rows
+from .evaluate import (_pesq_fn, gather_table, load_model, load_pair, pesq_or_nan, print_mean_std, reverse_start,
+                       sampler_arguments, sampler_kwargs)
+from .sampler import draw_seed
 
 SNRS = tuple(range(0, 41, 5))  # deep_eval.py:112
 LABELS = tuple(s - 5 for s in SNRS)
@@ -55,13 +58,10 @@ def snr_variants(x, y):
 
 
 def _batched_kind(model, sampler_type):
-    if model.snr_conditioned == "false" and model.model_type == "bbed" and sampler_type == "pc":
-        return "pc"
-    if model.snr_conditioned == "false" and model.model_type == "bbed" and sampler_type == "ode":
-        return "ode"
-    if model.snr_conditioned == "true" and model.model_type == "sebridge_v3":
-        return "snr_aligned"
-    return None
+    """ScoreModel._batch_route's answer for the sweep.  Its "pc" kind is one batched get_pc_sampler run, which
+    serves every corrector, `langevin` too, so the corrector is not asked about; enhance_variants looks at the
+    noise tape itself."""
+    return model._batch_route(sampler_type, "ald", {})
 
 
 def enhance_variants(model, ys, noise_rms, clean_rms=1.0, sampler_type="pc", predictor="reverse_diffusion",
@@ -76,7 +76,7 @@ def enhance_variants(model, ys, noise_rms, clean_rms=1.0, sampler_type="pc", pre
         kind = None  # an injected tape drives the per-variant path, as in ScoreModel._batch_route
     if kind == "ode":
         # the variants share a length: one batch, every row with its own adaptive steps and its own seed
-        seeds = [int(torch.randint(0, 2 ** 62, (1,)).item()) for _ in range(V)]
+        seeds = [draw_seed() for _ in range(V)]
         return np.stack(model.enhance_batch(list(ys), seeds=seeds, batch_size=V, max_frames=1 << 30,
                                             sampler_type="ode", N=N, **kwargs))
     if kind is None:
@@ -90,27 +90,19 @@ def enhance_variants(model, ys, noise_rms, clean_rms=1.0, sampler_type="pc", pre
                                      corrector_steps=corrector_steps, N=N, snr=snr, oracle=oracle,
                                      clean_rms=clean_rms, noise_rms=float(noise_rms[k]), **kw))
         return np.stack(out)
-    dev = torch.device("cuda", torch.cuda.current_device())
+    dev = ops.current_device()
     yb = torch.from_numpy(np.ascontiguousarray(ys)).to(dev)
-    mode = model.data_module.hip_mode()
     if kind == "pc":
-        nf = ops.absmax(yb)  # per-row max|y| (model.py:726)
-        Tp = L // 128 + 1
-        Tp = Tp + (64 - Tp % 64) % 64
-        Y = ops.stft(yb, 1.0, tpad=Tp, mode=mode, in_div=nf)
+        mode = model.data_module.hip_mode()
+        Y, nf, _ = enhance.front_end(yb, mode)  # per-row max|y| (model.py:726)
         sampler = model.get_pc_sampler(predictor, corrector, Y[:, None], N=N, corrector_steps=corrector_steps,
                                        snr=snr, noise_tape=noise_tape)
         sample, _ = sampler()
-        xh = ops.istft(sample[:, 0].contiguous(), L, mode=mode, out_scale=nf)
-        return xh.cpu().numpy()
-    from .enhance import SNRAlignedEnhancer
-    from sgmse.model import get_snr_model
-    enh = SNRAlignedEnhancer(model.dnn.hip(dev), snr_fn=lambda spec: get_snr_model().estimate_from_spec(spec),
-                             fixed_snr=float(model.fixed_snr), sigma_max=float(model.sigma_max),
-                             transform=model.data_module.transform_type)
+        return enhance.back_end(sample[:, 0], L, mode, nf).cpu().numpy()
+    enh = model.batched_enhancer("snr", model.dnn.hip(dev), oracle=oracle)
     est = np.asarray(noise_rms, np.float64) / float(clean_rms) if oracle else None  # model.py:722-724
     z = noise_tape(0) if noise_tape is not None else None
-    xh, _ = enh(yb, est_snr=est, noise=z, seed=int(torch.randint(0, 2 ** 62, (1,)).item()))
+    xh, _ = enh(yb, est_snr=est, noise=z, seed=draw_seed())
     return xh.cpu().numpy()
 
 
@@ -126,13 +118,7 @@ def deep_evaluate(model, test_dir, target_dir, sampler_type="pc", predictor="rev
     clean_dir, noisy_dir = join(test_dir, "clean"), join(test_dir, "noisy")
     for lab in LABELS:
         os.makedirs(join(target_dir, "{0:02d}".format(lab)), exist_ok=True)
-    if model.sde.__class__.__name__ == "OUVESDE":  # deep_eval.py:88-91
-        model.sde._T = reverse_starting_point
-    else:
-        model.sde.T = reverse_starting_point
-    N = int(reverse_starting_point / (1 / N))  # deep_eval.py:92-96
-    if force_N:
-        N = force_N
+    N = reverse_start(model, reverse_starting_point, N, force_N)  # deep_eval.py:88-96
     files = sorted(glob("{}/*.wav".format(noisy_dir)))
     a, b = sdist.shard_range(len(files), rank, world)
     pesq_fn = _pesq_fn()
@@ -151,34 +137,23 @@ def deep_evaluate(model, test_dir, target_dir, sampler_type="pc", predictor="rev
         row = []
         for k, lab in enumerate(LABELS):
             audio.write_wav(join(target_dir, "{0:02d}".format(lab), name), xh[k], 16000, bits=16)
-            p = float("nan")
-            if pesq_fn is not None:
-                try:
-                    p = float(pesq_fn(sr, x, xh[k], "wb"))
-                except Exception:  # deep_eval.py:134-137
-                    p = float("nan")
+            p = pesq_or_nan(pesq_fn, sr, x, xh[k])
             run[k] += p
             if verbose:
                 print("{0} | {1:.3f}".format(lab, run[k] / (cnt + 1)), flush=True)
             row.append(p)
-        if si_sdr:
-            dev = torch.device("cuda", torch.cuda.current_device())
+        if si_sdr or estoi:  # the enhanced variants and the one clean signal, cut to a common length, uploaded once
+            dev = ops.current_device()
             Lm = min(xh.shape[1], len(x))
-            xs = torch.from_numpy(np.ascontiguousarray(xh[:, :Lm], np.float32)).to(dev)
-            cl = torch.from_numpy(np.repeat(x[None, :Lm], len(LABELS), 0)).to(dev)
-            nz = torch.from_numpy(np.ascontiguousarray(ys[:, :Lm] - x[None, :Lm])).to(dev)
+            xs = pack_rows([h[:Lm] for h in xh])[0].to(dev)
+            cl = pack_rows([x[:Lm]] * len(LABELS))[0].to(dev)
+        if si_sdr:
+            nz = pack_rows(list(ys[:, :Lm] - x[None, :Lm]))[0].to(dev)
             row += [float(v) for v in ops.energy_ratios(xs, cl, nz)[:, 0].cpu().numpy()]
         if estoi:  # the nine variants against the one clean signal: one call
-            dev = torch.device("cuda", torch.cuda.current_device())
-            Lm = min(xh.shape[1], len(x))
-            xs = torch.from_numpy(np.ascontiguousarray(xh[:, :Lm], np.float32)).to(dev)
-            cl = torch.from_numpy(np.repeat(x[None, :Lm], len(LABELS), 0)).to(dev)
             row += [float(v) for v in ops.estoi(cl, xs, fs=sr).cpu().numpy()]
         rows.append(row)
-    dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
-    allm = sdist.gather_metrics(rows if rows else np.zeros((0, ncol)), len(files), rank, world,
-                                dev if world > 1 and sdist_backend_is_nccl() else torch.device("cpu"))
-    allm = allm.reshape(len(files), ncol).cpu().numpy()
+    allm = gather_table(rows, len(files), ncol, rank, world)
     data = {"filename": [os.path.basename(f) for f in files]}
     for k, lab in enumerate(LABELS):
         data[f"pesq_{lab}"] = [float(v) for v in allm[:, k]]
@@ -213,18 +188,7 @@ def main(argv=None):
     ap.add_argument("--destination_folder", type=str, required=True)
     ap.add_argument("--test_dir", type=str, required=True)
     ap.add_argument("--ckpt", type=str, required=True)
-    ap.add_argument("--sampler_type", type=str, choices=("pc", "ode"), default="pc")
-    ap.add_argument("--predictor", type=str, default="reverse_diffusion")
-    ap.add_argument("--reverse_starting_point", type=float, default=1.0)
-    ap.add_argument("--force_N", type=int, default=0)
-    ap.add_argument("--corrector", type=str, choices=("ald", "none"), default="ald")
-    ap.add_argument("--corrector_steps", type=int, default=1)
-    ap.add_argument("--snr", type=float, default=0.5)
-    ap.add_argument("--N", type=int, default=30)
-    ap.add_argument("--atol", type=float, default=1e-5)
-    ap.add_argument("--rtol", type=float, default=1e-5)
-    ap.add_argument("--timestep_type", type=str, default="linear")
-    ap.add_argument("--correct_stepsize", dest="correct_stepsize", action="store_true")
+    sampler_arguments(ap, correct_stepsize=True)
     ap.add_argument("--no_correct_stepsize", dest="correct_stepsize", action="store_false")
     ap.add_argument("--modeltype", type=str, choices=["bbed", "sebridge", "sebridge_v2", "sebridge_v3"],
                     default="bbed")  # parsed and unused, as in deep_eval.py:45
@@ -235,17 +199,9 @@ def main(argv=None):
                     help="add estoi_<label> columns, computed on the device (parity with pystoi unverified)")
     ap.add_argument("--resample", action="store_true",
                     help="bring clean / noisy files that are not at 16 kHz to 16 kHz on the device first")
-    ap.set_defaults(correct_stepsize=True)
     a = ap.parse_args(argv)
     rank, world, _ = sdist.init_from_env()
-    from sgmse.model import ScoreModel
-    model = ScoreModel.load_from_checkpoint(a.ckpt, base_dir="", batch_size=16, num_workers=0, kwargs=dict(gpu=False))
-    model.eval(no_ema=False)
-    model.cuda()
-    deep_evaluate(model, a.test_dir, a.destination_folder, sampler_type=a.sampler_type, predictor=a.predictor,
-                  corrector=a.corrector, corrector_steps=a.corrector_steps, snr=a.snr, N=a.N,
-                  reverse_starting_point=a.reverse_starting_point, force_N=a.force_N, atol=a.atol, rtol=a.rtol,
-                  timestep_type=a.timestep_type, correct_stepsize=a.correct_stepsize, oracle=a.oracle,
+    deep_evaluate(load_model(a.ckpt), a.test_dir, a.destination_folder, **sampler_kwargs(a), oracle=a.oracle,
                   rank=rank, world=world, batched=not a.per_variant, si_sdr=a.si_sdr, resample=a.resample,
                   **(dict(estoi=True) if a.estoi else {}))
 

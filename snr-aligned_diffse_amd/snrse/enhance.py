@@ -70,6 +70,37 @@ def crop_rows(x, ln):
     return torch.where(keep, x, torch.zeros((), device=x.device, dtype=x.dtype))
 
 
+def front_end(y, mode, lengths=None, div=None):
+    """The front end of every enhancement: y [B, L] f32 device -> (Y = STFT(y / div) padded to Tpad frames and
+    transformed by `mode`, div, ln).  div: per-row divisor, default max|y| (norm_factor, model.py:726).  lengths: a
+    ragged batch (ragged_lengths: the rows share Tpad), ln its ops.Lengths; None: ln is None and
+    Tpad = pad_frames(1 + L // 128)."""
+    ln, tpad = (None, pad_frames(1 + y.shape[1] // 128)) if lengths is None else ragged_lengths(lengths, y)
+    if div is None:
+        div = ops.absmax(y, lengths=ln)
+    return ops.stft(y, 1.0, tpad=tpad, mode=mode, in_div=div, lengths=ln), div, ln
+
+
+def back_end(x, L, mode, div, ln=None):
+    """front_end's inverse: spectrogram x [B, F, Tpad] -> waveforms [B, L] scaled by div, zero past each row's
+    length when ln is set."""
+    out = ops.istft(x.contiguous(), L, mode=mode, out_scale=div)
+    return out if ln is None else crop_rows(out, ln)
+
+
+def fused_step(net, Y, score_mode):
+    """The PC loop's score_step on an NCSNppHIP network: one evaluation (the pyramid) with the output head, the
+    score and the SDE update fused in one kernel."""
+
+    def step(x, tv, coef, z, seed, off):
+        pyr = net.pyramid(x, Y, tv)
+        xo, xm, _ = ops.score_update(pyr, net.W["out_w"], net.W["out_b"], tv, score_mode, x, Y, coef=coef, noise=z,
+                                     offset=off, **sampler.row_seed_kw(seed))
+        return xo, xm
+
+    return step
+
+
 class PCEnhancer:
     """PC-sampler enhancement of a batch of noisy waveforms with an NCSNppHIP network.
 
@@ -101,47 +132,29 @@ class PCEnhancer:
         self.stagger = bool(stagger)
         self._lane_streams = {}
 
+    def _step(self, Y, net):
+        """The score_step of one lane (a subclass may wrap it, as tools/agree3.py does to record the states)."""
+        return fused_step(net, Y, self.score_mode)
+
     def _iter(self, Y, noise, net=None):
         net = net or self.net
-
-        def step(x, tv, coef, z, seed, off):
-            pyr = net.pyramid(x, Y, tv)
-            xo, xm, _ = ops.score_update(pyr, net.W["out_w"], net.W["out_b"], tv, self.score_mode, x, Y,
-                                         coef=coef, noise=z, offset=off, **sampler.row_seed_kw(seed))
-            return xo, xm
 
         def score_tensor(x, tv):
             return net.score(x, Y, tv, self.score_mode)
 
-        return sampler.pc_sample_iter(step, Y, self.sde, N=self.N, eps=self.eps, snr=self.snr,
+        return sampler.pc_sample_iter(self._step(Y, net), Y, self.sde, N=self.N, eps=self.eps, snr=self.snr,
                                       predictor=self.predictor, corrector=self.corrector,
                                       corrector_steps=self.corrector_steps, noise=noise, score_tensor=score_tensor)
 
-    @staticmethod
-    def _drain(it):
-        while True:
-            try:
-                next(it)
-            except StopIteration as e:
-                return e.value
-
     def sample(self, Y, noise: sampler.NoiseSource | None = None):
-        policy = _guard.resolve(self.guard, self.net.dtype)
-        noise = noise or sampler.NoiseSource()
-        snap = _guard.snapshot(noise) if policy == "fallback" else None
-        x, nfe = self._sample(Y, noise)
-        rows = _guard.flagged_rows(x) if policy != "off" else []
-        if _guard.report(self, rows, policy, self.fallback_dtype, self.net.dtype):
-            fb = _guard.fallback_net(self.net, self.fallback_dtype)
-            for a, b, lane in _guard.run_noise(snap, rows, Y.shape[0]):
-                x[a:b] = self._drain(self._iter(Y[a:b].contiguous(), lane, net=fb))[0]
-        return x, nfe
+        return _guard.guarded(self, self._sample, Y, noise)
 
-    def _sample(self, Y, noise):
+    def _sample(self, Y, noise, net):
+        """The whole batch over the enhancer's streams; a guard re-run (another net) on one stream."""
         B = Y.shape[0]
-        nl = min(self.streams, B)
+        nl = min(self.streams, B) if net is self.net else 1
         if nl <= 1:
-            return self._drain(self._iter(Y, noise))
+            return sampler.drain(self._iter(Y, noise, net=net))
         cur = torch.cuda.current_stream(Y.device)
         bounds = [(B * h // nl, B * (h + 1) // nl) for h in range(nl)]
         lanes, lane_noise = [], []
@@ -182,18 +195,9 @@ class PCEnhancer:
         the [B, Lstride] buffer (what lies past L_b is never read); the rows must share Tpad (ragged_lengths),
         the result is zero past L_b.  A row's result equals its run alone up to GEMM summation order when
         `noise` is row-seeded (sampler.NoiseSource(row_seeds=...)) and the corrector is not `langevin`."""
-        B, L = y.shape
-        if lengths is not None:
-            ln, tpad = ragged_lengths(lengths, y)
-            nf = ops.absmax(y, lengths=ln)
-            Y = ops.stft(y, 1.0, tpad=tpad, mode=self.mode, in_div=nf, lengths=ln)
-            x, nfe = self.sample(Y, noise)
-            return crop_rows(ops.istft(x, L, mode=self.mode, out_scale=nf), ln), nfe
-        nf = ops.absmax(y)  # norm_factor = max|y| (model.py:726)
-        T = 1 + L // 128
-        Y = ops.stft(y, 1.0, tpad=pad_frames(T), mode=self.mode, in_div=nf)
+        Y, nf, ln = front_end(y, self.mode, lengths)
         x, nfe = self.sample(Y, noise)
-        return ops.istft(x, L, mode=self.mode, out_scale=nf), nfe
+        return back_end(x, y.shape[1], self.mode, nf, ln), nfe
 
 
 class ODEEnhancer:
@@ -248,9 +252,8 @@ class ODEEnhancer:
         B = Y.shape[0]
         prior = (0.0, 1.0, 0.0, self.sde.std(self.sde.T))  # build_schedule's prior coefficients
         z, off = noise.next(Y.numel())
-        rs = getattr(noise, "row_seeds", None)
         coef = torch.tensor([prior] * B, dtype=torch.float32, device=Y.device)
-        x0 = ops.axpby_noise(coef, y=Y, noise=z, offset=off, **sampler.row_seed_kw(noise.seed if rs is None else rs))
+        x0 = ops.axpby_noise(coef, y=Y, noise=z, offset=off, **sampler.row_seed_kw(noise.key))
         cache = {"rows": None, "Y": Y}
 
         def drift(t, x, rows, x32):
@@ -264,43 +267,29 @@ class ODEEnhancer:
         x = res.y.to(torch.complex64)
         if self.denoise:
             x = self._fused(net, x, Y, [self.eps] * B, self._denoise_coef)
+        if net is self.net:  # the whole-batch solve: the guard's re-runs stay out of last_stats
+            self.last_stats = {"evals": res.evals, "row_evals": res.row_evals, "status": [int(s) for s in res.status],
+                               "attempts": [len(h) + int(s == -2) for h, s in zip(res.history, res.status)]}
         return x, res
 
     def sample(self, Y, noise: sampler.NoiseSource | None = None):
         """Y [B, F, T] complex64 -> (x [B, F, T] complex64, nfev numpy [B]): each row's evaluation count as
         get_ode_sampler reports it for that row alone (2 + 6 x its attempts; the denoise step is not counted)."""
-        policy = _guard.resolve(self.guard, self.net.dtype)
-        noise = noise or sampler.NoiseSource()
-        snap = _guard.snapshot(noise) if policy == "fallback" else None
-        x, res = self._solve(Y, noise, self.net)
-        nfev = res.nfev.copy()
-        self.last_stats = {"evals": res.evals, "row_evals": res.row_evals, "status": [int(s) for s in res.status],
-                           "attempts": [len(h) + int(s == -2) for h, s in zip(res.history, res.status)]}
-        rows = []
-        if policy != "off":
-            rows = sorted(set(_guard.flagged_rows(x)) | {int(b) for b in np.nonzero(res.status == -2)[0]})
-        if _guard.report(self, rows, policy, self.fallback_dtype, self.net.dtype):
-            fb = _guard.fallback_net(self.net, self.fallback_dtype)
-            for a, b, lane in _guard.run_noise(snap, rows, Y.shape[0]):
-                x[a:b], r2 = self._solve(Y[a:b].contiguous(), lane, fb)
-                nfev[a:b] = r2.nfev
-        return x, nfev
+
+        def merge(res, again, a, b):
+            res.nfev[a:b] = again.nfev
+
+        x, res = _guard.guarded(self, self._solve, Y, noise, failed=lambda r: np.nonzero(r.status == -2)[0],
+                                merge=merge)
+        return x, res.nfev
 
     def __call__(self, y, noise=None, lengths=None):
         """y [B, L] f32 device -> (x_hat [B, L] f32, nfev numpy [B]).  lengths: a ragged batch under PCEnhancer's
         rule (rows sharing Tpad, the result zero past L_b); with a row-seeded `noise` a row's result is its run
         alone."""
-        B, L = y.shape
-        if lengths is not None:
-            ln, tpad = ragged_lengths(lengths, y)
-            nf = ops.absmax(y, lengths=ln)
-            Y = ops.stft(y, 1.0, tpad=tpad, mode=self.mode, in_div=nf, lengths=ln)
-            x, nfev = self.sample(Y, noise)
-            return crop_rows(ops.istft(x.contiguous(), L, mode=self.mode, out_scale=nf), ln), nfev
-        nf = ops.absmax(y)
-        Y = ops.stft(y, 1.0, tpad=pad_frames(1 + L // 128), mode=self.mode, in_div=nf)
+        Y, nf, ln = front_end(y, self.mode, lengths)
         x, nfev = self.sample(Y, noise)
-        return ops.istft(x.contiguous(), L, mode=self.mode, out_scale=nf), nfev
+        return back_end(x, y.shape[1], self.mode, nf, ln), nfev
 
 
 class SNRAlignedEnhancer:
@@ -329,9 +318,7 @@ class SNRAlignedEnhancer:
         (batching.snr_groups) and the NCSN++ pass stays whole.  row_seeds (one per row): row b's prior noise is
         Philox(row_seeds[b], e), what seed=row_seeds[b] draws for that row alone."""
         B, L = y.shape
-        ln = tpad = None
-        if lengths is not None:
-            ln, tpad = ragged_lengths(lengths, y)
+        ln = None if lengths is None else ragged_lengths(lengths, y)[0]
         nf = ops.absmax(y, lengths=ln)
         if est_snr is None and ln is not None:
             from .batching import snr_groups
@@ -348,17 +335,11 @@ class SNRAlignedEnhancer:
             est_snr = self.snr_fn(raw).reshape(B).double().cpu().numpy()
         t_hat = snap_t(est_snr, self.fixed_snr)
         div = nf * torch.from_numpy(normfac(t_hat, self.fixed_snr)).to(nf.device, torch.float32)
-        if ln is not None:
-            Y = ops.stft(y, 1.0, tpad=tpad, mode=self.mode, in_div=div, lengths=ln)
-        else:
-            Y = ops.stft(y, 1.0, tpad=pad_frames(1 + L // 128), mode=self.mode, in_div=div)
+        Y, div, ln = front_end(y, self.mode, ln, div)
         coef = torch.zeros(B, 4, dtype=torch.float32)
         coef[:, 1] = 1.0
         coef[:, 3] = torch.from_numpy(self.sigma_max * t_hat).float()
-        if row_seeds is not None:
-            X_T = ops.axpby_noise(coef.to(Y.device), y=Y, noise=noise, row_seeds=row_seeds)
-        else:
-            X_T = ops.axpby_noise(coef.to(Y.device), y=Y, noise=noise, seed=seed)
+        X_T = ops.axpby_noise(coef.to(Y.device), y=Y, noise=noise, seed=seed, row_seeds=row_seeds)
         tv = torch.from_numpy(t_hat).to(Y.device, torch.float32)
         sample = self.net.score(X_T, Y, tv, 1)
         # range guard (PCEnhancer): X_T does not depend on the network's format, so the flagged rows are one more
@@ -368,5 +349,4 @@ class SNRAlignedEnhancer:
         if _guard.report(self, rows, policy, self.fallback_dtype, self.net.dtype):
             fb = _guard.fallback_net(self.net, self.fallback_dtype)
             sample[rows] = fb.score(X_T[rows].contiguous(), Y[rows].contiguous(), tv[rows].contiguous(), 1)
-        out = ops.istft(sample.contiguous(), L, mode=self.mode, out_scale=div.contiguous())
-        return (out if ln is None else crop_rows(out, ln)), t_hat
+        return back_end(sample, L, self.mode, div, ln), t_hat

@@ -30,6 +30,9 @@ import numpy as np
 import torch
 
 from . import audio, dist as sdist
+from .batching import plan_batches
+from .evaluate import load_model, reverse_start, sampler_arguments, sampler_kwargs
+from .sampler import draw_seed
 
 CSV_COLUMNS = ("filename", "input_rate", "channels", "seconds", "output_rate")
 
@@ -53,7 +56,7 @@ def utterances(files):
 
 def draw_seeds(n):
     """n draws of the evaluation driver's per-file seed, in order."""
-    return [int(torch.randint(0, 2 ** 62, (1,)).item()) for _ in range(n)]
+    return [draw_seed() for _ in range(n)]
 
 
 def write_csv(files, output_rate, target_dir):
@@ -69,17 +72,10 @@ def enhance_files(model, noisy_dir, target_dir, batch_size=32, max_frames=16384,
                   snr=0.5, N=30, reverse_starting_point=1.0, force_N=0, atol=1e-5, rtol=1e-5,
                   timestep_type="linear", correct_stepsize=False, **enhance_kw):
     """-> the list_files() rows of every file (all ranks'); this rank's share is enhanced and written."""
-    from .batching import plan_batches
     if output_rate not in ("model", "input"):
         raise ValueError(f"enhance_files: output_rate is 'model' or 'input', got {output_rate!r}")
     os.makedirs(target_dir, exist_ok=True)
-    if model.sde.__class__.__name__ == "OUVESDE":  # as evaluate (eval.py:105-108)
-        model.sde._T = reverse_starting_point
-    else:
-        model.sde.T = reverse_starting_point
-    N = int(reverse_starting_point / (1 / N))
-    if force_N:
-        N = force_N
+    N = reverse_start(model, reverse_starting_point, N, force_N)
     files = list_files(noisy_dir)
     a, b = sdist.shard_range(len(files), rank, world)
     mine = files[a:b]
@@ -115,7 +111,6 @@ def enhance_files(model, noisy_dir, target_dir, batch_size=32, max_frames=16384,
 
 
 def parser():
-    from .evaluate import sampler_arguments
     ap = argparse.ArgumentParser(description="enhance a folder of noisy recordings on the MI355X path")
     ap.add_argument("--noisy_dir", type=str, required=True)
     ap.add_argument("--ckpt", type=str, required=True)
@@ -129,13 +124,9 @@ def parser():
 
 
 def main(argv=None):
-    from .evaluate import sampler_kwargs
     a = parser().parse_args(argv)
     rank, world, _ = sdist.init_from_env()
-    from sgmse.model import ScoreModel
-    model = ScoreModel.load_from_checkpoint(a.ckpt, base_dir="", batch_size=16, num_workers=0, kwargs=dict(gpu=False))
-    model.eval(no_ema=False)
-    model.cuda()
+    model = load_model(a.ckpt)
     if a.seed is not None:
         torch.manual_seed(a.seed)
     enhance_files(model, a.noisy_dir, a.destination_folder, batch_size=a.batch_size, output_rate=a.output_rate,

@@ -41,6 +41,8 @@ import numpy as np
 import torch
 
 from . import audio, dist as sdist, ops
+from .batching import pack_rows, plan_batches
+from .sampler import draw_seed
 
 METRICS = ("pesq", "si_sdr", "si_sir", "si_sar")
 
@@ -51,6 +53,45 @@ def _pesq_fn():
     except ImportError:
         return None
     return pesq
+
+
+def pesq_or_nan(fn, sr, ref, deg):
+    """Wide-band PESQ of `deg` against `ref` through fn (_pesq_fn()); NaN without the package and for any failure,
+    which is what the reference's try/except records (eval.py:147-150, deep_eval.py:134-137)."""
+    if fn is None:
+        return float("nan")
+    try:
+        return float(fn(sr, ref, deg, "wb"))
+    except Exception:
+        return float("nan")
+
+
+def reverse_start(model, reverse_starting_point, N, force_N=0):
+    """The drivers' prelude (eval.py:105-112): the reverse process starts at reverse_starting_point (OUVE keeps it
+    in _T) -> its step count, N scaled by it unless force_N is given."""
+    if model.sde.__class__.__name__ == "OUVESDE":
+        model.sde._T = reverse_starting_point
+    else:
+        model.sde.T = reverse_starting_point
+    N = int(reverse_starting_point / (1 / N))
+    return force_N if force_N else N
+
+
+def load_model(ckpt):
+    """The checkpoint as the command lines run it: EMA weights, eval mode, on the device."""
+    from sgmse.model import ScoreModel
+    model = ScoreModel.load_from_checkpoint(ckpt, base_dir="", batch_size=16, num_workers=0, kwargs=dict(gpu=False))
+    model.eval(no_ema=False)
+    model.cuda()
+    return model
+
+
+def gather_table(rows, n_files, ncol, rank, world):
+    """Every rank's per-file metric rows -> numpy [n_files, ncol] on every rank: one all_gather, on the device
+    under nccl and on the CPU otherwise."""
+    dev = ops.current_device() if world > 1 and sdist_backend_is_nccl() else torch.device("cpu")
+    allm = sdist.gather_metrics(rows if rows else np.zeros((0, ncol)), n_files, rank, world, dev)
+    return allm.reshape(n_files, ncol).cpu().numpy()
 
 
 def print_mean_std(data, decimal=2):
@@ -66,14 +107,8 @@ def print_mean_std(data, decimal=2):
 def score_files(x_hat, x, y, sr=16000, pesq_fn=None):
     """One file's metric row (pesq, si_sdr, si_sir, si_sar); x_hat, x, y 1-D numpy float32."""
     L = min(len(x_hat), len(x), len(y))
-    p = float("nan")
-    if pesq_fn is not None:
-        try:
-            p = float(pesq_fn(sr, x[:L], x_hat[:L], "wb"))
-        except Exception:  # the reference records NaN for any PESQ failure (eval.py:147-150)
-            p = float("nan")
-    dev = torch.device("cuda", torch.cuda.current_device())
-    sig = torch.from_numpy(np.stack([x_hat[:L], x[:L], y[:L] - x[:L]]).astype(np.float32)).to(dev)
+    p = pesq_or_nan(pesq_fn, sr, x[:L], x_hat[:L])
+    sig = torch.from_numpy(np.stack([x_hat[:L], x[:L], y[:L] - x[:L]]).astype(np.float32)).to(ops.current_device())
     er = ops.energy_ratios(sig[0:1], sig[1:2], sig[2:3])[0].cpu().numpy()
     return [p, float(er[0]), float(er[1]), float(er[2])]
 
@@ -112,13 +147,7 @@ def evaluate(model, test_dir, target_dir, sampler_type="pc", predictor="reverse_
     metrics = METRICS + ("estoi",) if estoi else METRICS
     clean_dir, noisy_dir = join(test_dir, "clean"), join(test_dir, "noisy")
     os.makedirs(join(target_dir, "all"), exist_ok=True)
-    if model.sde.__class__.__name__ == "OUVESDE":  # eval.py:105-108
-        model.sde._T = reverse_starting_point
-    else:
-        model.sde.T = reverse_starting_point
-    N = int(reverse_starting_point / (1 / N))
-    if force_N:
-        N = force_N
+    N = reverse_start(model, reverse_starting_point, N, force_N)
     clean_rms = noise_rms = None
     if oracle:  # per-file active RMS (eval.py:86-92 reads them from active_rms.txt)
         rows = [ln.split("\t") for ln in open(join(test_dir, "active_rms.txt")) if ln.strip()]
@@ -151,10 +180,7 @@ def evaluate(model, test_dir, target_dir, sampler_type="pc", predictor="reverse_
         if estoi:
             st = estoi_batch([np.asarray(x_hat, np.float32)], [x[0].numpy()], sr=sr)
             rows[-1] = list(rows[-1]) + [float(st[0])]
-    dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
-    allm = sdist.gather_metrics(rows if rows else np.zeros((0, len(metrics))), len(files), rank, world,
-                                dev if world > 1 and sdist_backend_is_nccl() else torch.device("cpu"))
-    allm = allm.reshape(len(files), len(metrics)).cpu().numpy()
+    allm = gather_table(rows, len(files), len(metrics), rank, world)
     data = {"filename": [os.path.basename(f) for f in files]}
     for k, m in enumerate(metrics):
         data[m] = [float(v) for v in allm[:, k]]
@@ -163,16 +189,19 @@ def evaluate(model, test_dir, target_dir, sampler_type="pc", predictor="reverse_
     return data
 
 
+def _upload_cropped(lists, Ls, dev=None):
+    """Lists of files (each a list of 1-D numpy float32), file b cut to Ls[b] samples -> [len(lists), B, max L]
+    float32 on the device, zero past each file's length: one upload."""
+    return torch.stack([pack_rows([s[:L] for s, L in zip(sigs, Ls)])[0] for sigs in lists]).to(
+        dev or ops.current_device())
+
+
 def score_batch(x_hat, x, y, dev=None):
     """SI-SDR / SI-SIR / SI-SAR of a batch of files of different lengths (lists of 1-D numpy float32) in one
     ragged snrse_energy_ratios launch: one [3, B, max L] upload, n = y - x formed on the device, file b scored
     over its first L_b = min(len x_hat, len x, len y) samples as score_files does.  -> ([B, 3] numpy f64, [L_b])."""
-    dev = dev or torch.device("cuda", torch.cuda.current_device())
     Ls = [min(len(h), len(c), len(n)) for h, c, n in zip(x_hat, x, y)]
-    sig = np.zeros((3, len(Ls), max(Ls)), np.float32)
-    for r, (h, c, n) in enumerate(zip(x_hat, x, y)):
-        sig[0, r, :Ls[r]], sig[1, r, :Ls[r]], sig[2, r, :Ls[r]] = h[:Ls[r]], c[:Ls[r]], n[:Ls[r]]
-    sd = torch.from_numpy(sig).to(dev)
+    sd = _upload_cropped((x_hat, x, y), Ls, dev)
     return ops.energy_ratios(sd[0], sd[1], sd[2] - sd[1], lengths=Ls).cpu().numpy(), Ls
 
 
@@ -180,12 +209,8 @@ def estoi_batch(x_hat, x, dev=None, sr=16000):
     """ESTOI of a batch of files of different lengths (lists of 1-D numpy float32: enhanced, clean) at `sr` Hz in
     one ragged snrse.ops.estoi call: one [2, B, max L] upload, file b scored over its first
     L_b = min(len x_hat, len x) samples as score_files crops them.  -> [B] numpy f64 (one read-back)."""
-    dev = dev or torch.device("cuda", torch.cuda.current_device())
     Ls = [min(len(h), len(c)) for h, c in zip(x_hat, x)]
-    sig = np.zeros((2, len(Ls), max(Ls)), np.float32)
-    for r, (h, c) in enumerate(zip(x_hat, x)):
-        sig[0, r, :Ls[r]], sig[1, r, :Ls[r]] = c[:Ls[r]], h[:Ls[r]]
-    sd = torch.from_numpy(sig).to(dev)
+    sd = _upload_cropped((x, x_hat), Ls, dev)
     return ops.estoi(sd[0], sd[1], lengths=Ls, fs=sr).cpu().numpy()
 
 
@@ -195,13 +220,12 @@ def _evaluate_batched(model, files, a, b, clean_dir, target_dir, pesq_fn, batch_
     batch one load, one enhance_batch call, the 16-bit files and one ragged energy_ratios launch with n = y - x
     formed on the device; PESQ on the host, file by file.  The seeds are drawn first, one per file in file order:
     the draws of the per-file loop under the same torch RNG state."""
-    from .batching import plan_batches
     idx = list(range(a, b))
-    seeds = [int(torch.randint(0, 2 ** 62, (1,)).item()) for _ in idx]
+    seeds = [draw_seed() for _ in idx]
     lens = [audio.info(files[i])[0] for i in idx]
     if resample:  # the plan is made of the 16 kHz lengths, still from the headers alone
         lens = [audio.resampled_length(L, audio.info(files[i])[2], audio.MODEL_RATE) for L, i in zip(lens, idx)]
-    dev = torch.device("cuda", torch.cuda.current_device())
+    dev = ops.current_device()
     rows = [None] * len(idx)
     oracle = kw["oracle"]
     for batch in plan_batches(lens, batch_size, max_frames):
@@ -217,12 +241,7 @@ def _evaluate_batched(model, files, a, b, clean_dir, target_dir, pesq_fn, batch_
             audio.write_wav(join(target_dir, "all", nm), h, 16000, bits=16)
         er, Ls = score_batch(x_hat, [x[0].numpy() for x, _ in xs], [y[0].numpy() for y in ys], dev)
         for r, k in enumerate(batch):
-            p = float("nan")
-            if pesq_fn is not None:
-                try:
-                    p = float(pesq_fn(xs[r][1], xs[r][0][0, :Ls[r]].numpy(), x_hat[r][:Ls[r]], "wb"))
-                except Exception:  # as score_files: NaN for any PESQ failure (eval.py:147-150)
-                    p = float("nan")
+            p = pesq_or_nan(pesq_fn, xs[r][1], xs[r][0][0, :Ls[r]].numpy(), x_hat[r][:Ls[r]])
             rows[k] = [p, float(er[r, 0]), float(er[r, 1]), float(er[r, 2])]
         if estoi:  # files of one batch may differ in rate without --resample: one call per rate
             for sr in sorted({s for _, s in xs}):
@@ -255,8 +274,9 @@ def write_tables(data, target_dir):
             f.write(f"ESTOI: {print_mean_std(data['estoi'])} \n")
 
 
-def sampler_arguments(ap):
-    """The sampler options of eval.py (shared with snrse.enhance_files)."""
+def sampler_arguments(ap, correct_stepsize=False):
+    """The sampler options of eval.py (shared with snrse.enhance_files and, where --correct_stepsize defaults to
+    on and --no_correct_stepsize turns it off, with snrse.deep_evaluate)."""
     ap.add_argument("--sampler_type", type=str, choices=("pc", "ode"), default="pc")
     ap.add_argument("--predictor", type=str, default="reverse_diffusion")
     ap.add_argument("--reverse_starting_point", type=float, default=1.0)
@@ -268,7 +288,7 @@ def sampler_arguments(ap):
     ap.add_argument("--atol", type=float, default=1e-5)
     ap.add_argument("--rtol", type=float, default=1e-5)
     ap.add_argument("--timestep_type", type=str, default="linear")
-    ap.add_argument("--correct_stepsize", action="store_true")
+    ap.add_argument("--correct_stepsize", action="store_true", default=correct_stepsize)
 
 
 def sampler_kwargs(a):
@@ -295,12 +315,8 @@ def main(argv=None):
                     help="add the ESTOI column, computed on the device (snrse.ops.estoi; pystoi parity unverified)")
     a = ap.parse_args(argv)
     rank, world, _ = sdist.init_from_env()
-    from sgmse.model import ScoreModel
-    model = ScoreModel.load_from_checkpoint(a.ckpt, base_dir="", batch_size=16, num_workers=0, kwargs=dict(gpu=False))
-    model.eval(no_ema=False)
-    model.cuda()
-    evaluate(model, a.test_dir, a.destination_folder, **sampler_kwargs(a), oracle=a.oracle, rank=rank, world=world,
-             batch_size=a.batch_size, resample=a.resample, **(dict(estoi=True) if a.estoi else {}))
+    evaluate(load_model(a.ckpt), a.test_dir, a.destination_folder, **sampler_kwargs(a), oracle=a.oracle, rank=rank,
+             world=world, batch_size=a.batch_size, resample=a.resample, **(dict(estoi=True) if a.estoi else {}))
 
 
 if __name__ == "__main__":

@@ -192,8 +192,8 @@ def validate(model, limit_val_batches=None, rank=0, world=1, seeder=None, estoi=
     finally:
         model.train(True)
     if world > 1:
-        from . import dist as sdist
-        device = torch.device("cuda", torch.cuda.current_device())
+        from . import dist as sdist, ops
+        device = ops.current_device()
         tot, err, cnt = sdist.sum_over_ranks([tot, err, cnt], device)
     if cnt:
         out["valid_loss"] = tot / cnt
@@ -288,11 +288,11 @@ def fit(model, max_epochs=None, max_steps=None, accumulate_grad_batches=1, gradi
     per_batch = bool(batch_seeding) or world > 1
     reducer = sdist = None
     if world > 1:
-        from . import dist as sdist
+        from . import dist as sdist, ops
         if not sdist.dist.is_initialized() or sdist.dist.get_world_size() != world:
             raise RuntimeError(f"snrse.fit: world = {world} needs torch.distributed initialised with that many "
                                "ranks (snrse.dist.init_from_env() in every rank's process)")
-        device = torch.device("cuda", torch.cuda.current_device())
+        device = ops.current_device()
         # torch DDP's construction: every replica starts from rank 0's module state (after a resume, which
         # every rank loads onto its own device, this copies equal values)
         sdist.broadcast_tensors(list(model.state_dict().values()), device)

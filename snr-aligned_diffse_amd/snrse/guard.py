@@ -64,7 +64,7 @@ def snapshot(noise: sampler.NoiseSource | None):
     """A NoiseSource as the caller's is now (seed, tape, row seeds, draw index), left untouched by the call it is
     taken for."""
     noise = noise or sampler.NoiseSource()
-    snap = sampler.NoiseSource(noise.seed, noise.tape, getattr(noise, "row_seeds", None))
+    snap = sampler.NoiseSource(noise.seed, noise.tape, noise.row_seeds)
     snap.i = noise.i
     return snap
 
@@ -107,3 +107,25 @@ def report(owner, rows, policy, fallback_dtype, net_dtype):
                       f"in {fallback_dtype} (python -m snrse.range_check shows where the range is left)",
                       RangeFallbackWarning, stacklevel=3)
     return True
+
+
+def guarded(owner, solve, Y, noise=None, failed=None, merge=None):
+    """The guard flow of a sampling enhancer (owner: .guard, .fallback_dtype, .net, .last_guard):
+    solve(Y, noise, net) -> (x, aux) on the whole batch with owner.net; the rows of x that are not finite, and the
+    rows failed(aux) names, are flagged and reported; under "fallback" each contiguous run [a, b) of them is solved
+    again through the fallback network with the draws the whole-batch run took for it, x[a:b] replaced and
+    merge(aux, aux_rerun, a, b) called.  -> (x, aux)."""
+    policy = resolve(owner.guard, owner.net.dtype)
+    noise = noise or sampler.NoiseSource()
+    snap = snapshot(noise) if policy == "fallback" else None
+    x, aux = solve(Y, noise, owner.net)
+    rows = []
+    if policy != "off":
+        rows = sorted(set(flagged_rows(x)) | {int(b) for b in (failed(aux) if failed else ())})
+    if report(owner, rows, policy, owner.fallback_dtype, owner.net.dtype):
+        fb = fallback_net(owner.net, owner.fallback_dtype)
+        for a, b, lane in run_noise(snap, rows, Y.shape[0]):
+            x[a:b], again = solve(Y[a:b].contiguous(), lane, fb)
+            if merge:
+                merge(aux, again, a, b)
+    return x, aux

@@ -73,6 +73,11 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
+def current_device():
+    """The current HIP device with its index: what the .device of a tensor on it compares equal to."""
+    return torch.device("cuda", torch.cuda.current_device())
+
+
 def _ws_alloc(dev):
     mb = int(os.environ.get("SNRSE_WORKSPACE_MB", "128"))
     return (torch.empty(mb << 18, dtype=torch.float32, device=dev) if mb > 0 else None), mb
@@ -131,7 +136,7 @@ def _tls_contexts(dev):
 def context(dev=None, lane=None):
     """The calling thread's current LaunchContext on `dev` (lane: that lane's context, created on first
     use; default: the lane selected by use_workspace_lane, initially 0)."""
-    dev = torch.device("cuda", torch.cuda.current_device()) if dev is None else torch.device(dev)
+    dev = current_device() if dev is None else torch.device(dev)
     ctxs = _tls_contexts(dev)
     if lane is None:
         lane = _TLS.lane.get(dev, 0)
@@ -369,7 +374,7 @@ def new_stats(x_or_shape, C=None):
     if C is None:
         B, C, dev = x_or_shape.shape[0], x_or_shape.shape[-1], x_or_shape.device
     else:
-        B, dev = x_or_shape, torch.device("cuda", torch.cuda.current_device())
+        B, dev = x_or_shape, current_device()
     st = _arena_stack()
     if st and st[-1].device == torch.device(dev):
         t = st[-1].take(B * STAT_SLOTS * C * 2)
@@ -578,6 +583,16 @@ def _row_seeds(row_seeds, B, dev):
     return row_seeds.to(dev).contiguous()
 
 
+def _noise_key(seed, row_seeds, B, dev):
+    """How a noise op keys its draws -> (entry suffix, key argument, tensor to keep until the launch is issued):
+    "" and the batch-keyed seed as a uint64, or "_rs" and the pointer to the row seeds.  The two entries of an op
+    take the key in the same position (_lib.SIGNATURES)."""
+    if row_seeds is None:
+        return "", int(seed) & (2**64 - 1), None
+    rs = _row_seeds(row_seeds, B, dev)
+    return "_rs", rs.data_ptr(), rs
+
+
 def score_update(pyr, out_w, out_b, t, score_mode, x, y=None, coef=None, noise=None, seed=0, offset=0,
                  want_score=False, x_out=None, xmean_out=None, row_seeds=None):
     """Output head + score + optional SDE step.  Returns (x_out, x_mean, score).  pyr: float32, or bfloat16 (the
@@ -595,16 +610,10 @@ def score_update(pyr, out_w, out_b, t, score_mode, x, y=None, coef=None, noise=N
         xmean_out = torch.empty_like(x) if xmean_out is None else xmean_out
     else:
         x_out = xmean_out = None
-    if row_seeds is not None:
-        rs = _row_seeds(row_seeds, B, x.device)
-        _lib.call("snrse_score_update_rs", pyr.data_ptr(), int(pyr.dtype == torch.float32), out_w.data_ptr(),
-                  out_b.data_ptr(), t.data_ptr(), int(score_mode), B, HW, x.data_ptr(), _ptr(y), _ptr(noise),
-                  rs.data_ptr(), int(offset), _ptr(coef), _ptr(x_out), _ptr(xmean_out), _ptr(score), _stream())
-        return x_out, xmean_out, score
-    _lib.call("snrse_score_update", pyr.data_ptr(), int(pyr.dtype == torch.float32), out_w.data_ptr(),
-              out_b.data_ptr(), t.data_ptr(), int(score_mode), B, HW, x.data_ptr(), _ptr(y), _ptr(noise),
-              int(seed) & (2**64 - 1), int(offset), _ptr(coef), _ptr(x_out), _ptr(xmean_out), _ptr(score),
-              _stream())
+    sfx, key, _keep = _noise_key(seed, row_seeds, B, x.device)
+    _lib.call("snrse_score_update" + sfx, pyr.data_ptr(), int(pyr.dtype == torch.float32), out_w.data_ptr(),
+              out_b.data_ptr(), t.data_ptr(), int(score_mode), B, HW, x.data_ptr(), _ptr(y), _ptr(noise), key,
+              int(offset), _ptr(coef), _ptr(x_out), _ptr(xmean_out), _ptr(score), _stream())
     return x_out, xmean_out, score
 
 
@@ -615,13 +624,9 @@ def sde_update(x, coef, y=None, score=None, noise=None, seed=0, offset=0, x_out=
     HW = x.shape[-2] * x.shape[-1]
     x_out = torch.empty_like(x) if x_out is None else x_out
     xmean_out = torch.empty_like(x) if xmean_out is None else xmean_out
-    if row_seeds is not None:  # row-seeded draws (score_update): offset is the draw index
-        rs = _row_seeds(row_seeds, B, x.device)
-        _lib.call("snrse_sde_update_rs", x.data_ptr(), _ptr(y), _ptr(score), _ptr(noise), rs.data_ptr(), int(offset),
-                  coef.data_ptr(), B, HW, x_out.data_ptr(), xmean_out.data_ptr(), _stream())
-        return x_out, xmean_out
-    _lib.call("snrse_sde_update", x.data_ptr(), _ptr(y), _ptr(score), _ptr(noise), int(seed) & (2**64 - 1),
-              int(offset), coef.data_ptr(), B, HW, x_out.data_ptr(), xmean_out.data_ptr(), _stream())
+    sfx, key, _keep = _noise_key(seed, row_seeds, B, x.device)
+    _lib.call("snrse_sde_update" + sfx, x.data_ptr(), _ptr(y), _ptr(score), _ptr(noise), key, int(offset),
+              coef.data_ptr(), B, HW, x_out.data_ptr(), xmean_out.data_ptr(), _stream())
     return x_out, xmean_out
 
 
@@ -631,13 +636,9 @@ def axpby_noise(coef, x=None, y=None, noise=None, seed=0, offset=0, like=None, r
     B = ref.shape[0]
     HW = ref.shape[-2] * ref.shape[-1]
     out = torch.empty_like(ref)
-    if row_seeds is not None:  # row-seeded draws (score_update): offset is the draw index
-        rs = _row_seeds(row_seeds, B, ref.device)
-        _lib.call("snrse_axpby_noise_rs", _ptr(x), _ptr(y), _ptr(noise), rs.data_ptr(), int(offset), coef.data_ptr(),
-                  B, HW, out.data_ptr(), _stream())
-        return out
-    _lib.call("snrse_axpby_noise", _ptr(x), _ptr(y), _ptr(noise), int(seed) & (2**64 - 1), int(offset),
-              coef.data_ptr(), B, HW, out.data_ptr(), _stream())
+    sfx, key, _keep = _noise_key(seed, row_seeds, B, ref.device)
+    _lib.call("snrse_axpby_noise" + sfx, _ptr(x), _ptr(y), _ptr(noise), key, int(offset), coef.data_ptr(), B, HW,
+              out.data_ptr(), _stream())
     return out
 
 
@@ -702,7 +703,17 @@ def absmax(sig, lengths=None):
     return out
 
 
-_RESAMPLE_TAPS = {}  # (up, down, device) -> (phase-major taps on the device, half): the default filter, built once
+_TAPS = {}  # (filter design, up, down, device) -> (phase-major taps on the device, half), built once
+
+
+def cached_taps(design, up, down, dev):
+    """design(up, down)'s filter (snrse.audio.resample_taps, stoi_resample_taps) as resample_poly takes a caller's
+    cache: (phase-major taps on `dev`, half), built on first use."""
+    key = (design, up, down, dev)
+    if key not in _TAPS:
+        pm, half = phase_major_taps(design(up, down), up)
+        _TAPS[key] = (torch.from_numpy(pm).to(dev), half)
+    return _TAPS[key]
 
 
 def phase_major_taps(w, up):
@@ -754,12 +765,8 @@ def resample_poly(x, up, down, lengths=None, taps=None):
     tp, half = None, 0
     if (up, down) != (1, 1):
         if taps is None:
-            key = (up, down, x.device)
-            if key not in _RESAMPLE_TAPS:
-                from .audio import resample_taps
-                pm, half = phase_major_taps(resample_taps(up, down), up)
-                _RESAMPLE_TAPS[key] = (torch.from_numpy(pm).to(x.device), half)
-            tp, half = _RESAMPLE_TAPS[key]
+            from .audio import resample_taps
+            tp, half = cached_taps(resample_taps, up, down, x.device)
         elif isinstance(taps, tuple):  # (phase-major taps on the device, half): a caller's own cache, used as it is
             tp, half = taps
         else:
@@ -768,9 +775,6 @@ def resample_poly(x, up, down, lengths=None, taps=None):
     _lib.call("snrse_resample_poly", _ptr(x) if Lin else None, ln_dev.data_ptr(), B, Lin, up, down, half, _ptr(tp),
               y.data_ptr(), y.shape[1], _stream())
     return y, out_dev
-
-
-_STOI_TAPS = {}  # (up, down, device) -> ESTOI's resampling filter (snrse.audio.stoi_resample_taps) on the device
 
 
 def estoi(x, y, lengths=None, fs=16000, return_info=False):
@@ -794,12 +798,9 @@ def estoi(x, y, lengths=None, fs=16000, return_info=False):
     from .audio import STOI_RATE, rational, stoi_resample_taps
     up, down = rational(int(fs), STOI_RATE)
     if (up, down) != (1, 1):
-        key = (up, down, x.device)
-        if key not in _STOI_TAPS:
-            pm, half = phase_major_taps(stoi_resample_taps(up, down), up)
-            _STOI_TAPS[key] = (torch.from_numpy(pm).to(x.device), half)
-        x, ln_dev = resample_poly(x, up, down, lengths=ln.host, taps=_STOI_TAPS[key])
-        y, _ = resample_poly(y, up, down, lengths=ln.host, taps=_STOI_TAPS[key])
+        taps = cached_taps(stoi_resample_taps, up, down, x.device)
+        x, ln_dev = resample_poly(x, up, down, lengths=ln.host, taps=taps)
+        y, _ = resample_poly(y, up, down, lengths=ln.host, taps=taps)
         L = x.shape[1]
     nbytes = int(_lib.load().snrse_estoi_workspace(B, L))
     work = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
@@ -960,18 +961,8 @@ def upfirdn2d(inp, kernel, up=1, down=1, pad=(0, 0)):
     """Reference-signature upfirdn2d (op/upfirdn2d.py:145-156) on [N, C, H, W]."""
     _dev(inp, kernel)
     N, Cc, H, W = inp.shape
-    kh, kw = kernel.shape
-    x = inp.reshape(N * Cc, H, W, 1).contiguous()
-    oh = (H * up + pad[0] + pad[1] - kh) // down + 1
-    ow = (W * up + pad[0] + pad[1] - kw) // down + 1
-    out = torch.empty(N * Cc, oh, ow, 1, device=inp.device, dtype=inp.dtype)
-    k = kernel.to(torch.float32).contiguous()
-    dt = UPFIRDN_DTYPES.get(inp.dtype)
-    if dt is None:
-        raise TypeError(f"upfirdn2d: unsupported dtype {inp.dtype} (float, double, half, bfloat16)")
-    _lib.call("snrse_upfirdn2d", x.data_ptr(), out.data_ptr(), k.data_ptr(), N * Cc, H, W, 1, kh, kw, up, up,
-              down, down, pad[0], pad[1], pad[0], pad[1], dt, _stream())
-    return out.view(N, Cc, oh, ow)
+    out = _upfirdn_raw(inp.reshape(N * Cc, H, W, 1), kernel, up, up, down, down, pad[0], pad[1], pad[0], pad[1])
+    return out.view(N, Cc, out.shape[1], out.shape[2])
 
 
 def _upfirdn_raw(x4, k, upx, upy, dnx, dny, px0, px1, py0, py1):

@@ -102,12 +102,11 @@ def _load_sd(ckpt):
 
 
 def _inputs(args, dev):
-    from . import enhance, formula, ops
+    from . import enhance, formula
     if args.wav:
         from . import audio
         y = audio.load(args.wav)[0][:1].contiguous().to(dev)  # first channel, [1, L]
-        T = 1 + y.shape[1] // 128
-        return ops.stft(y, 1.0, tpad=enhance.pad_frames(T), mode=1, in_div=ops.absmax(y))
+        return enhance.front_end(y, 1)[0]
     return (torch.from_numpy(formula.normal_tensor("range_check.y", (args.batch, 256, args.frames), True)) * 0.5).to(dev)
 
 
@@ -123,8 +122,8 @@ def main(argv=None):
     ap.add_argument("--frames", type=int, default=64)
     ap.add_argument("--sigma", type=float, default=0.5, help="x_t = y + sigma t z")
     args = ap.parse_args(argv)
-    from . import enhance, formula, ncsnpp
-    dev = torch.device("cuda", torch.cuda.current_device())
+    from . import enhance, formula, ncsnpp, ops
+    dev = ops.current_device()
     sd, what = _load_sd(args.ckpt)
     net = ncsnpp.NCSNppHIP(sd, dtype=DTYPES[args.dtype], device=dev)
     Y = _inputs(args, dev).contiguous()

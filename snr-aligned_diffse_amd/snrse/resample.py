@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from . import audio, ops
+from .batching import pack_rows
 
 
 def as_signal(y):
@@ -39,13 +40,9 @@ def convert(sigs, rates_in, rates_out, on_device=False):
     out = list(sigs)
     if not groups or set(groups) == {None}:
         return out
-    dev = torch.device("cuda", torch.cuda.current_device())
+    dev = ops.current_device()
     for key, rows in groups.items():
-        rs = [as_signal(sigs[i]) for i in rows]
-        lens = [int(s.numel()) for s in rs]
-        buf = torch.zeros(len(rows), max(max(lens), 1), dtype=torch.float32)
-        for r, s in enumerate(rs):
-            buf[r, :lens[r]] = s
+        buf, lens = pack_rows([sigs[i] for i in rows])
         y = buf.to(dev)
         if key is not None:
             y, _ = ops.resample_poly(y, *audio.rational(*key), lengths=lens)

@@ -142,6 +142,12 @@ class NoiseSource:
                 row_seeds = row_seeds.cuda()
         self.row_seeds = row_seeds
 
+    @property
+    def key(self):
+        """What the in-kernel draws are keyed by, and what a score_step gets as `seed`: the int seed, or the
+        row-seed tensor (row_seed_kw turns either into the ops' keywords)."""
+        return self.seed if self.row_seeds is None else self.row_seeds
+
     def next(self, numel):
         i = self.i
         self.i += 1
@@ -159,7 +165,7 @@ class LaneNoise(NoiseSource):
     parent: the seeds of rows [a, b) and the parent's draw index."""
 
     def __init__(self, parent: NoiseSource, a, b, rows):
-        rs = getattr(parent, "row_seeds", None)
+        rs = parent.row_seeds
         super().__init__(parent.seed, None, None if rs is None else rs[a:b].contiguous())
         self.parent_tape, self.a, self.b, self.rows = parent.tape, a, b, rows
         self.i = parent.i  # continue where the parent's earlier draws left off
@@ -181,6 +187,21 @@ def row_seed_kw(seed):
     return {"row_seeds": seed} if torch.is_tensor(seed) else {"seed": seed}
 
 
+def draw_seed():
+    """One noise seed from torch's default generator (so torch.manual_seed reproduces a run): the draw every
+    enhancement path and driver makes per utterance."""
+    return int(torch.randint(0, 2 ** 62, (1,)).item())
+
+
+def drain(it):
+    """Run a pc_sample_iter generator to its end -> what it returns, (x_result, nfe)."""
+    while True:
+        try:
+            next(it)
+        except StopIteration as e:
+            return e.value
+
+
 def pc_sample(score_step, Y, sde: SDESpec, N=30, eps=0.03, snr=0.5, predictor="reverse_diffusion",
               corrector="ald", corrector_steps=1, noise: NoiseSource | None = None, denoise=True,
               score_tensor=None, Y_prior=None, probability_flow=False):
@@ -189,14 +210,9 @@ def pc_sample(score_step, Y, sde: SDESpec, N=30, eps=0.03, snr=0.5, predictor="r
     row-seeded NoiseSource `seed` is the int64 seed tensor and `offset` the draw index: see row_seed_kw);
     score_tensor(x, t_vec) -> complex score (only needed for the Langevin corrector).
     Returns (x_result, nfe)."""
-    it = pc_sample_iter(score_step, Y, sde, N=N, eps=eps, snr=snr, predictor=predictor, corrector=corrector,
-                        corrector_steps=corrector_steps, noise=noise, denoise=denoise, score_tensor=score_tensor,
-                        Y_prior=Y_prior, probability_flow=probability_flow)
-    while True:
-        try:
-            next(it)
-        except StopIteration as e:
-            return e.value
+    return drain(pc_sample_iter(score_step, Y, sde, N=N, eps=eps, snr=snr, predictor=predictor, corrector=corrector,
+                                corrector_steps=corrector_steps, noise=noise, denoise=denoise,
+                                score_tensor=score_tensor, Y_prior=Y_prior, probability_flow=probability_flow))
 
 
 def pc_sample_lockstep(lanes, on_first=None):
@@ -242,8 +258,7 @@ def pc_sample_iter(score_step, Y, sde: SDESpec, N=30, eps=0.03, snr=0.5, predict
     ttab = torch.tensor(np.repeat(np.asarray([t for _, t, _ in steps], dtype=np.float32)[:, None], B, axis=1),
                         device=dev)
     z, off = noise.next(numel)
-    rs = getattr(noise, "row_seeds", None)
-    key = noise.seed if rs is None else rs  # what score_step gets as `seed` (row_seed_kw turns it into keywords)
+    key = noise.key
     x = ops.axpby_noise(ctab[-1], y=Y if Y_prior is None else Y_prior, noise=z, offset=off, **row_seed_kw(key))
     x_mean = x
     ci = 0

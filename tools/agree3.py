@@ -19,7 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "snr-aligned_diffse_amd")]
 import paritycheck  # noqa: E402
 from conftest import formula_sd  # noqa: E402
-from snrse import ncsnpp, ops, sampler  # noqa: E402
+from snrse import ncsnpp, sampler  # noqa: E402
 from snrse.enhance import PCEnhancer  # noqa: E402
 from test_gpu_c2_path import _clips  # noqa: E402
 
@@ -27,19 +27,14 @@ from test_gpu_c2_path import _clips  # noqa: E402
 class RecordingPC(PCEnhancer):
     """PCEnhancer that keeps the PC state x entering every network evaluation (the whole batch, on the device)."""
 
-    def _iter(self, Y, noise):
-        net, rec = self.net, self.rec
+    def _step(self, Y, net):
+        fused, rec = super()._step(Y, net), self.rec
 
-        def step(x, tv, coef, z, seed, off):
+        def step(x, *args):
             rec.append(x.detach().clone())
-            pyr = net.pyramid(x, Y, tv)
-            xo, xm, _ = ops.score_update(pyr, net.W["out_w"], net.W["out_b"], tv, self.score_mode, x, Y,
-                                         coef=coef, noise=z, seed=seed, offset=off)
-            return xo, xm
+            return fused(x, *args)
 
-        return sampler.pc_sample_iter(step, Y, self.sde, N=self.N, eps=self.eps, snr=self.snr,
-                                      predictor=self.predictor, corrector=self.corrector,
-                                      corrector_steps=self.corrector_steps, noise=noise)
+        return step
 
 
 def run(y, dt, gemm):

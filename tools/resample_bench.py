@@ -42,9 +42,9 @@ def spread(v):
 
 
 def kernel_timing(x, up, down, reps, repeats):
-    from snrse import _lib, ops
+    from snrse import _lib, audio, ops
     y, _ = ops.resample_poly(x, up, down)  # builds and caches the taps; y is the output buffer of the timed launches
-    taps, half = ops._RESAMPLE_TAPS[(up, down, x.device)]
+    taps, half = ops.cached_taps(audio.resample_taps, up, down, x.device)
     B, L = x.shape
     ln = torch.full((B,), L, dtype=torch.int32, device=x.device)
     stream = torch.cuda.current_stream().cuda_stream
