@@ -306,6 +306,35 @@ int snrse_resample_poly(const float* x, const int* lengths, int B, long long str
                         const float* taps, float* y, long long stride_out, hipStream_t stream);
 int snrse_resample_poly_block(void);
 
+/* Recordings of any length (csrc/window.hip, snrse/longform.py): a recording is cut into overlapping windows of W
+ * samples, the windows run as rows of the batched enhancers, and their results are joined by a cross-fade over the
+ * first V samples of every window of a recording but its first.
+ *
+ * snrse_window_gather: src [R][stride] f32 ragged with lengths [R] int32 on the device; table [nwin][3] int32 on the
+ * device = (source row, start, length <= W) per window -> out [nwin][W] f32, out[j][i] = src[row_j][start_j + i]
+ * for i < length_j and start_j + i < L_row, zero otherwise.  Nothing at or past a source row's length is read, and a
+ * table entry that names no row of src gives a row of zeros.
+ *
+ * snrse_window_merge: win [nwin][W] f32, starts [nwin] int32 (sample at which each window begins in its recording),
+ * silent [nwin] uint8, first [R + 1] int32 (recording r owns the windows first[r] .. first[r + 1] - 1, whose starts
+ * ascend from 0), lengths [R] int32, fade [V] f32 = sin^2(pi (i + 1/2) / (2 V)), all on the device -> out
+ * [R][stride_out] f32.  For sample n < L_r, with k the last window of r whose start s_k <= n and i = n - s_k:
+ *   k is not r's first window and i < V:  out = fma(fade[i], x_k[i], (1 - fade[i]) * x_{k-1}[n - s_{k-1}])
+ *   otherwise:                            out = x_k[i]
+ * where x_j[.] is win[j][.], or 0 without reading it when silent[j] is set.  What a window holds past the next
+ * one's fade is never read; samples [L_r, stride_out) are written as zero; a one-window recording is a copy.  One
+ * thread per output sample and one fixed fp32 expression: no atomics, the same bits on every launch and for a
+ * recording launched alone.  The CALLER sees to windows that cover their recording (each gap <= W - V); a sample
+ * no window covers is written as zero.
+ *
+ * Both return hipErrorInvalidValue before any HIP call for a NULL pointer or a size <= 0; the merge also for
+ * 4 V > W. */
+int snrse_window_gather(const float* src, const int* lengths, int R, long long stride, const int* table, int nwin,
+                        int W, float* out, hipStream_t stream);
+int snrse_window_merge(const float* win, int nwin, int W, const int* starts, const unsigned char* silent,
+                       const int* first, const int* lengths, int R, const float* fade, int V, float* out,
+                       long long stride_out, hipStream_t stream);
+
 /* ESTOI, the extended short-time objective intelligibility measure (Jensen & Taal 2016 with pystoi's conventions;
  * csrc/estoi.hip), of a ragged batch: x clean and y processed, [B][stride] f32 at 10 kHz, lengths [B] int32 on the
  * device (clamped to [0, stride]) -> out [B] f64 and info [B][2] int32 = (K, S).  For one row of length L, with the

@@ -408,7 +408,7 @@ class ScoreModel(nn.Module):
     def enhance_batch(self, ys, seeds=None, batch_size=32, max_frames=16384, sampler_type="pc",
                       predictor="reverse_diffusion", corrector="ald", N=30, corrector_steps=1, snr=0.5, oracle=False,
                       clean_rms=None, noise_rms=None, range_guard="auto", sample_rates=None, output_rate="model",
-                      **kwargs):
+                      window_frames=None, overlap_frames=64, **kwargs):
         """enhance() for a list of noisy utterances of different lengths (each [L], [1, L], numpy or tensor) ->
         list of numpy [L_i] in input order.  Utterances whose spectrograms pad to the same frame count share a
         ragged batch (snrse.batching.plan_batches: at most batch_size rows and max_frames frames per batch).
@@ -434,8 +434,25 @@ class ScoreModel(nn.Module):
         ops.resample_poly launch per distinct rate), and everything above -- the batch plan, max|y|, the results'
         lengths -- is that of the 16 kHz signals, resampled_length(L_i, rate_i, 16000) samples each.  The seeds
         are drawn as without it, before any device work.  output_rate "model" returns the 16 kHz waveforms,
-        "input" resamples each back to its own rate and cuts it to exactly L_i samples."""
+        "input" resamples each back to its own rate and cuts it to exactly L_i samples.
+
+        window_frames: None (every utterance is one network input, however long), or the frame count of a window
+        (a multiple of 64; 512 is the flagship shape): recordings of any length.  Every utterance is cut, at 16 kHz
+        and on the device, into overlapping windows (snrse.longform: one window when it has at most
+        (window_frames - 1) 128 samples, and then its result is bit for bit the unwindowed one), the windows of all
+        utterances run as rows of the same batched enhancers -- each with its own max|y|, SNR estimate and seed
+        (the utterance's for its window 0, longform.window_seed(seed, k) for window k) -- and one
+        ops.window_merge launch cross-fades them over overlap_frames frames.  No enhancer call sees more than
+        batch_size rows or max_frames frames, so device memory does not grow with the recording beyond about three
+        copies of its samples.  A window of digital silence (max|y| = 0) is not sent to the network and counts as
+        zeros.  last_guard["flagged"] lists utterances as before, last_guard["flagged_windows"] the
+        (utterance, window) pairs."""
         from snrse import batching
+        if window_frames is not None:
+            return self._enhance_windowed(ys, seeds, batch_size, max_frames, sample_rates, output_rate,
+                                          window_frames, overlap_frames, oracle, clean_rms, noise_rms, range_guard,
+                                          dict(sampler_type=sampler_type, predictor=predictor, corrector=corrector,
+                                               N=N, corrector_steps=corrector_steps, snr=snr), kwargs)
         n = len(ys)
         route = self._batch_route(sampler_type, corrector, kwargs)
         if sample_rates is not None:
@@ -504,9 +521,105 @@ class ScoreModel(nn.Module):
             self.last_guard = dict(enh.last_guard or {}, flagged=sorted(flagged))
         return out
 
+    def _enhance_windowed(self, ys, seeds, batch_size, max_frames, sample_rates, output_rate, window_frames,
+                          overlap_frames, oracle, clean_rms, noise_rms, range_guard, skw, kwargs):
+        """enhance_batch(window_frames=...): plan (snrse.longform) -> one gather -> the windows through the route's
+        enhancer, batch by batch, their results written back over the windows -> one merge.  skw: the sampler
+        keywords of enhance()."""
+        from snrse import audio, batching, longform, resample
+        W, V, _ = longform.geometry(window_frames, overlap_frames)  # bad arguments fail before any device work
+        n = len(ys)
+        route = self._batch_route(skw["sampler_type"], skw["corrector"], kwargs)
+        if sample_rates is not None:
+            if output_rate not in ("model", "input"):
+                raise ValueError(f"enhance_batch: output_rate is 'model' or 'input', got {output_rate!r}")
+            if len(sample_rates) != n:
+                raise ValueError(f"enhance_batch: {len(sample_rates)} sample rates for {n} utterances")
+        if route is not None and seeds is None:
+            seeds = [_samp.draw_seed() for _ in range(n)]
+        if route is not None and len(seeds) != n:
+            raise ValueError(f"enhance_batch: {len(seeds)} seeds for {n} utterances")
+        if oracle and (clean_rms is None or noise_rms is None or len(clean_rms) != n or len(noise_rms) != n):
+            raise ValueError("enhance_batch(oracle=True) takes clean_rms and noise_rms, one value per utterance")
+        self.data_module.hip_mode()
+        if n == 0:
+            return []
+        sigs = [resample.as_signal(y) for y in ys]
+        lens_in = [int(s.numel()) for s in sigs]
+        if sample_rates is not None:
+            sigs = resample.convert(sigs, sample_rates, audio.MODEL_RATE, on_device=True)
+        lens = [int(s.numel()) for s in sigs]
+        for i, L in enumerate(lens):
+            if L < batching.MIN_LENGTH:
+                raise ValueError(f"enhance_batch: utterance {i} has {L} samples; the STFT's reflect padding needs at "
+                                 f"least {batching.MIN_LENGTH}")
+        plan = longform.Plan(lens, window_frames, overlap_frames)
+        dev = ops.current_device()
+        # the recordings go up once; every window is cut on the device, and the enhancers' results overwrite it
+        src = sigs[0].reshape(1, -1) if n == 1 else batching.pack_rows(sigs)[0]  # one recording needs no packing
+        wins = ops.window_gather(src.to(dev).contiguous(), lens, plan.table, W)
+        del sigs, src
+        wl = np.asarray(plan.win_lengths, np.int64)
+        silent = ops.absmax(wins, lengths=wl).cpu().numpy() == 0  # the call's one read-back before the results
+        live = [j for j in range(len(plan)) if not silent[j]]
+        wseeds = plan.seeds(seeds) if route is not None else None
+        flagged = []
+        ode_stats = self.last_ode_stats = []
+        guard = {}
+        if route is None:
+            for j in live:
+                u = plan.utt[j]
+                y = wins[j, :wl[j]].cpu().reshape(1, -1)
+                x = self.enhance(y, y, oracle=oracle, clean_rms=clean_rms[u] if oracle else 1,
+                                 noise_rms=noise_rms[u] if oracle else 1, range_guard=range_guard, **skw, **kwargs)
+                flagged += [(u, plan.k[j])] if (self.last_guard or {}).get("flagged") else []
+                guard = self.last_guard or {}
+                wins[j, :wl[j]] = torch.from_numpy(np.asarray(x, np.float32)).to(dev)
+        elif live:
+            with self._compute_format(self.RANGE_FALLBACK if self._range_fallback else self.dnn.compute_dtype):
+                enh = self.batched_enhancer(route, self.dnn.hip(dev), range_guard, skw["predictor"],
+                                            skw["corrector"], skw["N"], skw["corrector_steps"], skw["snr"], oracle,
+                                            kwargs.get("rtol", 1e-5), kwargs.get("atol", 1e-5))
+                for rows in batching.plan_batches([wl[j] for j in live], batch_size, max_frames):
+                    js = [live[r] for r in rows]
+                    ln = [int(wl[j]) for j in js]
+                    idx = torch.tensor(js, device=dev)
+                    yb = wins[idx][:, :max(ln)].contiguous()
+                    rs = torch.tensor([wseeds[j] for j in js], dtype=torch.int64, device=dev)
+                    if route in ("pc", "ode"):
+                        xb, nfe = enh(yb, noise=_samp.NoiseSource(row_seeds=rs), lengths=ln)
+                        if route == "ode":
+                            ode_stats.append(dict(enh.last_stats, files=[plan.utt[j] for j in js],
+                                                  windows=[plan.k[j] for j in js], nfev=[int(v) for v in nfe]))
+                    else:
+                        est = [float(noise_rms[plan.utt[j]]) / float(clean_rms[plan.utt[j]]) for j in js] \
+                            if oracle else None
+                        xb, _ = enh(yb, est_snr=est, lengths=ln, row_seeds=rs)
+                    flagged += [(plan.utt[js[r]], plan.k[js[r]]) for r in (enh.last_guard or {}).get("flagged", [])]
+                    wins[idx, :max(ln)] = xb
+                guard = enh.last_guard or {}
+        out = ops.window_merge(wins, plan.starts, plan.first, lens, V, silent=torch.from_numpy(silent),
+                               stride_out=max(lens)).cpu().numpy()
+        self.last_guard = dict(guard, flagged=sorted({u for u, _ in flagged}), flagged_windows=sorted(flagged))
+        self.last_windows = plan.counts()
+        out = [out[r, :lens[r]].copy() for r in range(n)]
+        if sample_rates is not None and output_rate == "input":
+            back = resample.convert(out, audio.MODEL_RATE, sample_rates)
+            out = [np.asarray(h)[:L] for h, L in zip(back, lens_in)]
+        return out
+
+    def enhance_long(self, y, sample_rate=16000, **kw):
+        """One recording of any length, y [L] / [1, L] at `sample_rate` -> numpy [L'] (at 16 kHz, or with
+        output_rate="input" at its own rate and length): enhance_batch([y], sample_rates=[sample_rate],
+        window_frames=512, ...) -- windows of 512 frames (8.2 s) cross-faded over overlap_frames = 64 (0.5 s) unless
+        the keywords say otherwise."""
+        kw.setdefault("window_frames", 512)
+        return self.enhance_batch([y], sample_rates=[int(sample_rate)], **kw)[0]
+
     RANGE_FALLBACK = "bf16"   # compute_dtype enhance() falls back to when fp16 overflows
     _range_fallback = False   # set by the first hit: this model then runs RANGE_FALLBACK
     last_guard = None         # the latest enhance() call's guard record (snrse.guard.report)
+    last_windows = None       # the latest enhance_batch(window_frames=...) call's window count per utterance
     last_ode_stats = None     # the latest enhance_batch() call's ODE batches: ODEEnhancer.last_stats + files, nfev
 
     @contextlib.contextmanager

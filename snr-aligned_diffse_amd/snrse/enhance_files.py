@@ -10,13 +10,22 @@ into a 16-bit PCM file of the same name and channel count under <destination_fol
 --output_rate input at the file's own rate and frame count.  _enhanced.csv lists name, input rate, channels,
 seconds and output rate of every file.
 
+--window_frames F (off by default) is for recordings longer than the network's training crops -- meetings, podcasts,
+anything from about ten seconds up: without it a file is one network input, whose memory grows with its length (and
+with its square in the attention) until the device runs out.  With it every channel is cut into overlapping windows
+of F frames (512 = 8.2 s is the flagship shape), the windows of a call share the ragged batches, and their results
+are cross-faded over --overlap_frames frames (ScoreModel.enhance_batch(window_frames=...), snrse.longform); a file
+of at most (F - 1) 128 samples at 16 kHz is enhanced exactly as without the flag, and _enhanced.csv gets a `windows`
+column (windows per channel).
+
 The seeds are drawn first, one torch.randint(0, 2**62) per (file, channel), in file order then channel order: for
 a folder of 16 kHz mono files these are the draws, the plan and the calls of snrse.evaluate --batch_size B, and the
 files written are byte for byte those it writes into <destination_folder>/all.  Files shard contiguously over
 ranks (snrse.dist.shard_range); rank 0 writes the csv, which needs the headers only.
 
     python -m snrse.enhance_files --noisy_dir DIR --ckpt CKPT --destination_folder OUT \\
-        [--batch_size 32] [--output_rate model|input] [--seed S] [--N 30 --sampler_type pc ...]
+        [--batch_size 32] [--output_rate model|input] [--seed S] [--N 30 --sampler_type pc ...] \\
+        [--window_frames 512 [--overlap_frames 64]]
 """
 from __future__ import annotations
 
@@ -29,7 +38,7 @@ from os.path import join
 import numpy as np
 import torch
 
-from . import audio, dist as sdist
+from . import audio, dist as sdist, longform
 from .batching import plan_batches
 from .evaluate import load_model, reverse_start, sampler_arguments, sampler_kwargs
 from .sampler import draw_seed
@@ -59,21 +68,32 @@ def draw_seeds(n):
     return [draw_seed() for _ in range(n)]
 
 
-def write_csv(files, output_rate, target_dir):
+def write_csv(files, output_rate, target_dir, window=None):
+    """window: None, or (window_frames, overlap_frames): one more column, the windows of each channel."""
     with open(join(target_dir, "_enhanced.csv"), "w") as f:
-        f.write(",".join(CSV_COLUMNS) + "\n")
+        f.write(",".join(CSV_COLUMNS + (("windows",) if window else ())) + "\n")
         for path, n, ch, sr in files:
             ro = sr if output_rate == "input" else audio.MODEL_RATE
-            f.write(f"{os.path.basename(path)},{sr},{ch},{n / sr!r},{ro}\n")
+            row = f"{os.path.basename(path)},{sr},{ch},{n / sr!r},{ro}"
+            if window:
+                W, V, _ = longform.geometry(*window)
+                row += f",{len(longform.window_starts(audio.resampled_length(n, sr, audio.MODEL_RATE), W, V))}"
+            f.write(row + "\n")
 
 
 def enhance_files(model, noisy_dir, target_dir, batch_size=32, max_frames=16384, output_rate="model", rank=0,
                   world=1, sampler_type="pc", predictor="reverse_diffusion", corrector="ald", corrector_steps=1,
                   snr=0.5, N=30, reverse_starting_point=1.0, force_N=0, atol=1e-5, rtol=1e-5,
-                  timestep_type="linear", correct_stepsize=False, **enhance_kw):
-    """-> the list_files() rows of every file (all ranks'); this rank's share is enhanced and written."""
+                  timestep_type="linear", correct_stepsize=False, window_frames=None, overlap_frames=64,
+                  **enhance_kw):
+    """-> the list_files() rows of every file (all ranks'); this rank's share is enhanced and written.
+    window_frames / overlap_frames: ScoreModel.enhance_batch's (None: every channel is one network input)."""
     if output_rate not in ("model", "input"):
         raise ValueError(f"enhance_files: output_rate is 'model' or 'input', got {output_rate!r}")
+    window = None
+    if window_frames is not None:
+        longform.geometry(window_frames, overlap_frames)
+        window = (window_frames, overlap_frames)
     os.makedirs(target_dir, exist_ok=True)
     N = reverse_start(model, reverse_starting_point, N, force_N)
     files = list_files(noisy_dir)
@@ -85,6 +105,8 @@ def enhance_files(model, noisy_dir, target_dir, batch_size=32, max_frames=16384,
               **enhance_kw)
     # settings without a batched enhancer run enhance_batch's per-utterance loop, which draws as it goes
     seeds = draw_seeds(len(utts)) if model._batch_route(sampler_type, corrector, enhance_kw) is not None else None
+    if window:  # the calls are planned as without it, by the channels' whole lengths; the windows inside each call
+        kw.update(window_frames=window_frames, overlap_frames=overlap_frames)
     lens = [audio.resampled_length(mine[k][1], mine[k][3], audio.MODEL_RATE) for k, _ in utts]
     done = {k: [None] * f[2] for k, f in enumerate(mine)}
     for batch in plan_batches(lens, batch_size, max_frames):
@@ -94,7 +116,8 @@ def enhance_files(model, noisy_dir, target_dir, batch_size=32, max_frames=16384,
             if k not in loaded:
                 loaded[k] = audio.load(mine[k][0])[0]
         hs = model.enhance_batch([loaded[utts[u][0]][utts[u][1]] for u in batch],
-                                 seeds=None if seeds is None else [seeds[u] for u in batch], batch_size=len(batch),
+                                 seeds=None if seeds is None else [seeds[u] for u in batch],
+                                 batch_size=batch_size if window else len(batch),  # windows: rows per enhancer call
                                  max_frames=max_frames, sample_rates=[mine[utts[u][0]][3] for u in batch],
                                  output_rate=output_rate, **kw)
         for u, h in zip(batch, hs):
@@ -106,7 +129,7 @@ def enhance_files(model, noisy_dir, target_dir, batch_size=32, max_frames=16384,
                 audio.write_wav(join(target_dir, os.path.basename(path)), x[0] if ch == 1 else np.stack(x, 1),
                                 sr if output_rate == "input" else audio.MODEL_RATE, bits=16)
     if rank == 0:
-        write_csv(files, output_rate, target_dir)
+        write_csv(files, output_rate, target_dir, window)
     return files
 
 
@@ -119,6 +142,11 @@ def parser():
     ap.add_argument("--output_rate", type=str, choices=("model", "input"), default="model",
                     help="write at 16 kHz (model) or at each file's own rate and frame count (input)")
     ap.add_argument("--seed", type=int, default=None, help="torch.manual_seed before the noise seeds are drawn")
+    ap.add_argument("--window_frames", type=int, default=None,
+                    help="enhance long recordings in overlapping windows of this many frames (a multiple of 64; 512 "
+                         "= 8.2 s is the flagship shape); off by default")
+    ap.add_argument("--overlap_frames", type=int, default=64,
+                    help="frames over which neighbouring windows are cross-faded (with --window_frames)")
     sampler_arguments(ap)
     return ap
 
@@ -130,7 +158,8 @@ def main(argv=None):
     if a.seed is not None:
         torch.manual_seed(a.seed)
     enhance_files(model, a.noisy_dir, a.destination_folder, batch_size=a.batch_size, output_rate=a.output_rate,
-                  rank=rank, world=world, **sampler_kwargs(a))
+                  rank=rank, world=world, window_frames=a.window_frames, overlap_frames=a.overlap_frames,
+                  **sampler_kwargs(a))
 
 
 if __name__ == "__main__":

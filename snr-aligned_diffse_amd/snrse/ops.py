@@ -777,6 +777,83 @@ def resample_poly(x, up, down, lengths=None, taps=None):
     return y, out_dev
 
 
+def _i32(v, dev, shape=None):
+    """A table of integers (sequence / numpy, or an int32 tensor already on `dev`) -> contiguous int32 on `dev`."""
+    if torch.is_tensor(v) and v.dtype == torch.int32 and v.device == dev:
+        t = v.contiguous()
+    else:
+        t = torch.from_numpy(np.ascontiguousarray(np.asarray(v.cpu() if torch.is_tensor(v) else v, dtype=np.int32)))
+        t = t.to(dev)
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"snrse: a table of shape {tuple(t.shape)} where {tuple(shape)} is expected")
+    return t
+
+
+def window_gather(src, lengths, table, W):
+    """Cut windows out of a ragged batch of recordings: src [R, stride] f32 on the device with lengths [R]; table
+    [nwin, 3] = (source row, start, length <= W) per window -> [nwin, W] f32, row j holding
+    src[row_j, start_j : start_j + length_j] and zeros after it (snrse_window_gather).  Nothing at or past a
+    recording's length is read.  The tables may be sequences / numpy (uploaded here) or int32 device tensors."""
+    _dev(src)
+    if src.dim() != 2 or src.dtype != torch.float32 or not src.is_contiguous():
+        raise TypeError("snrse: window_gather takes a contiguous [R, stride] float32 batch")
+    R, stride = src.shape
+    tb = _i32(table, src.device)
+    if tb.dim() != 2 or tb.shape[1] != 3 or tb.shape[0] < 1:
+        raise ValueError(f"snrse: window_gather takes a [nwin, 3] table, got {tuple(tb.shape)}")
+    ln = _i32(lengths, src.device, (R,))
+    out = torch.empty(tb.shape[0], int(W), device=src.device, dtype=torch.float32)
+    _lib.call("snrse_window_gather", src.data_ptr(), ln.data_ptr(), R, stride, tb.data_ptr(), tb.shape[0], int(W),
+              out.data_ptr(), _stream())
+    return out
+
+
+def fade_table(V, dev):
+    """snrse.longform.fade_table(V) on the device (fp64 on the host, rounded to fp32 once, cached per V)."""
+    key = ("fade", int(V), dev)
+    if key not in _TAPS:
+        from .longform import fade_table as host_table
+        _TAPS[key] = torch.from_numpy(host_table(V).astype(np.float32)).to(dev)
+    return _TAPS[key]
+
+
+def window_merge(win, starts, first, lengths, V, silent=None, stride_out=None, fade=None):
+    """Join window results into their recordings (snrse_window_merge; the rule stands in include/snrse.h): win
+    [nwin, W] f32 on the device, starts [nwin], first [R + 1] (recording r owns windows first[r] .. first[r + 1] - 1),
+    lengths [R], silent [nwin] bool / uint8 or None (a flagged window counts as zeros and is not read), fade the
+    [V] f32 table on the device (None: fade_table(V)) -> [R, stride_out] f32, stride_out default max(lengths), zero
+    past each length.  One launch, no read-back."""
+    _dev(win)
+    if win.dim() != 2 or win.dtype != torch.float32 or not win.is_contiguous():
+        raise TypeError("snrse: window_merge takes a contiguous [nwin, W] float32 batch")
+    nwin, W = win.shape
+    V = int(V)
+    if V < 1 or 4 * V > W:
+        raise ValueError(f"snrse: window_merge needs 0 < 4 V <= W, got V = {V}, W = {W}")
+    dev = win.device
+    fs = _i32(first, dev)
+    R = fs.numel() - 1
+    if R < 1:
+        raise ValueError("snrse: window_merge takes first offsets of R + 1 >= 2 entries")
+    st, ln = _i32(starts, dev, (nwin,)), _i32(lengths, dev, (R,))
+    if silent is None:
+        sl = torch.zeros(nwin, dtype=torch.uint8, device=dev)
+    else:
+        sl = torch.as_tensor(silent).to(dev).ne(0).to(torch.uint8).contiguous()
+        if sl.shape != (nwin,):
+            raise ValueError(f"snrse: {tuple(sl.shape)} silence flags for {nwin} windows")
+    if fade is None:
+        fade = fade_table(V, dev)
+    if fade.shape != (V,) or fade.dtype != torch.float32 or fade.device != dev:
+        raise ValueError(f"snrse: window_merge takes a [{V}] float32 fade table on the windows' device")
+    if stride_out is None:
+        stride_out = int(np.asarray(lengths.cpu() if torch.is_tensor(lengths) else lengths).max())
+    out = torch.empty(R, max(int(stride_out), 1), device=dev, dtype=torch.float32)
+    _lib.call("snrse_window_merge", win.data_ptr(), nwin, W, st.data_ptr(), sl.data_ptr(), fs.data_ptr(),
+              ln.data_ptr(), R, fade.contiguous().data_ptr(), V, out.data_ptr(), out.shape[1], _stream())
+    return out
+
+
 def estoi(x, y, lengths=None, fs=16000, return_info=False):
     """ESTOI (Jensen & Taal 2016 with pystoi's conventions; the definition stands at snrse_estoi in
     include/snrse.h) of a ragged batch: x clean, y processed, [B, L] f32 on the device at `fs` Hz, row b valid on
