@@ -545,6 +545,40 @@ int snrse_adam_ema_scaled(const void* tensors, const int* chunk_tensor, const lo
 int snrse_grad_pack(const void* tensors, const int* chunk_tensor, const long long* chunk_start, int nchunks,
                     const long long* flat_off, float scale, float* flat, hipStream_t stream);
 
+/* ---- Fixed-SNR dataset preparation (snrse.snrize; csrc/snrize.hip): active-level analysis of a clean / noise
+ * pair and its remix to a target active SNR.  Ragged batches: c, n [B][stride] f32 with lengths [B] (clamped to
+ * [0, stride] on the device; nothing at or past a row's length is read).  Windows of W samples, non-overlapping
+ * from sample 0, the last one possibly partial (its mean is over its true length); nWmax = ceil(stride / W).
+ * Window k of a row is active iff sqrt(mean n_k^2) > 10^(-50/20) (max |n| + eps), eps = 2^-52: by the noise alone.
+ * No f64 atomics and a fixed order of every sum: a row's results are the same bits whichever rows share its launch
+ * and however its buffer is aligned.  Every entry returns hipErrorInvalidValue, before any HIP call, for a NULL
+ * required pointer, B, stride or W <= 0, stride >= 2^31 or a float pointer that is not 4-B aligned. */
+
+/* wsums [B][nWmax][2] f64 = (sum c^2, sum n^2) of every window a row has (the others are left unwritten);
+ * partials [B][ceil(nWmax / P)][5] f64 = (sum c, sum n, sum c^2, sum n^2, sum c n) over each block's P windows,
+ * P = snrse_active_windows_per_block(); nmax [B] f32 = max |n| of the row. */
+int snrse_active_window_sums(const float* c, const float* n, const int* lengths, int B, long long stride, int W,
+                             double* wsums, double* partials, float* nmax, hipStream_t stream);
+int snrse_active_windows_per_block(void);
+/* From those three: out [B][5] f64 = clean_rms, noise_rms (sqrt of the sum over the active windows / their sample
+ * count, windows in ascending order; both eps when no window is active), the number of active windows, the Pearson
+ * coefficient of c and n over the whole row (0 when either has no variance) and the gain
+ * g = clean_rms / noise_rms * 10^(-snr_db[b] / 20) that brings the pair to snr_db[b] dB active SNR. */
+int snrse_active_finalize(const double* wsums, const double* partials, const float* nmax, const int* lengths, int B,
+                          long long stride, int W, const double* snr_db, double* out, hipStream_t stream);
+/* n_out = gf n and y_out = fma(gf, n, c) with gf = (float)gain[b * gain_stride] (y_out is the once-rounded
+ * gf n + c, not c + n_out rounded again), both [B][stride] f32 and zero from the row's length on;
+ * ymax [B] f32 = max |y_out| of the row. */
+int snrse_snr_mix(const float* c, const float* n, const int* lengths, int B, long long stride, const double* gain,
+                  int gain_stride, float* n_out, float* y_out, float* ymax, hipStream_t stream);
+/* Clip guard and 16-bit output: scale[b] = ymax[b] > 0.99 ? (0.99 - eps) / ymax[b] : 1 (f64, computed on the
+ * device); each of c, n1, y times (float)scale[b] into c_f, n_f, y_f (f32; may alias their inputs) and, of those
+ * products x, clip(round_half_even(32768 x), -32768, 32767) into c_q, n_q, y_q (int16).  Any of the six outputs
+ * may be NULL; all are [B][stride] and zero from the row's length on. */
+int snrse_scale_to_pcm16(const float* c, const float* n1, const float* y, const int* lengths, int B, long long stride,
+                         const float* ymax, float* c_f, float* n_f, float* y_f, short* c_q, short* n_q, short* y_q,
+                         double* scale, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -95,12 +95,18 @@ SIGNATURES = {
     "snrse_rk45_combine": [_vp, _vp, _vp, _vp, _i, _i, _i, _ll, _vp, _vp, _vp],
     "snrse_rk45_rownorm": [_vp, _vp, _i, _i, _vp, _vp, _vp, _d, _d, _i, _i, _ll, _vp, _vp, _vp],
     "snrse_rk45_accept": [_vp, _vp, _vp, _ll, _vp, _vp, _ll, _i, _vp],
+    # fixed-SNR dataset preparation (csrc/snrize.hip)
+    "snrse_active_window_sums": [_vp, _vp, _vp, _i, _ll, _i, _vp, _vp, _vp, _vp],
+    "snrse_active_finalize": [_vp, _vp, _vp, _vp, _i, _ll, _i, _vp, _vp, _vp],
+    "snrse_snr_mix": [_vp, _vp, _vp, _i, _ll, _vp, _i, _vp, _vp, _vp, _vp],
+    "snrse_scale_to_pcm16": [_vp, _vp, _vp, _vp, _i, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
 }
 HOUSEKEEPING = {"snrse_abi_version": ([], _i), "snrse_build_id": ([], C.c_char_p), "snrse_error_string": ([_i], C.c_char_p),
                 "snrse_device_name": ([C.c_char_p, _i], _i), "snrse_snrnet_workspace": ([_i, _i], C.c_size_t),
                 "snrse_snrnet_train_workspace": ([_i, _i], C.c_size_t),
                 "snrse_rk45_rownorm_blocks": ([_i, _ll], _i), "snrse_resample_poly_block": ([], _i),
                 "snrse_estoi_workspace": ([_i, _ll], C.c_size_t), "snrse_estoi_block": ([], _i),
+                "snrse_active_windows_per_block": ([], _i),
                 "snrse_ctx_create": ([], _vp), "snrse_ctx_destroy": ([_vp], None)}
 
 _lib = None

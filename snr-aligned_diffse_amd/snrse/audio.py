@@ -147,11 +147,15 @@ def stoi_resample_taps(up: int, down: int) -> np.ndarray:
 
 
 def write_wav(path: str, x: np.ndarray, sr: int = 16000, bits: int = 16):
-    """Write [frames] or [frames, channels] float audio as PCM16 or float32 (test fixtures, outputs)."""
+    """Write [frames] or [frames, channels] float audio as PCM16 or float32 (test fixtures, outputs).  An int16
+    array with bits = 16 is written as it is: samples already converted (ops.scale_to_pcm16)."""
     x = np.asarray(x)
     x = x[:, None] if x.ndim == 1 else x
     ch = x.shape[1]
-    if bits == 16:
+    if bits == 16 and x.dtype == np.int16:
+        data = x.astype("<i2").tobytes()
+        tag = _PCM
+    elif bits == 16:
         data = np.clip(np.round(x * 32768.0), -32768, 32767).astype("<i2").tobytes()
         tag = _PCM
     elif bits == 32:

@@ -30,6 +30,8 @@ FILE_FLAGS = {name: ["-fno-slp-vectorize"] for name in ("conv.hip", "conv_head.h
 FILE_FLAGS["ode.hip"] = ["-ffp-contract=off"]
 # The cross-fade of window.hip is one written-out expression (fma(t, a, (1 - t) b)) whose error bound counts its roundings
 FILE_FLAGS["window.hip"] = ["-ffp-contract=off"]
+# The remix of snrize.hip is two written-out expressions (g n and fma(g, n, c)) whose error bound counts their roundings
+FILE_FLAGS["snrize.hip"] = ["-ffp-contract=off"]
 
 
 def _sources(csrc=CSRC):

@@ -888,6 +888,124 @@ def estoi(x, y, lengths=None, fs=16000, return_info=False):
     return (out, info) if return_info else out
 
 
+def _snr_pair(what, clean, noise, lengths):
+    """The checks the dataset-preparation ops share -> (B, stride, Lengths)."""
+    if clean.dim() != 2 or clean.shape != noise.shape or clean.dtype != torch.float32 or noise.dtype != torch.float32:
+        raise TypeError(f"snrse: {what} takes two [B, L] float32 batches of one shape")
+    B, L = clean.shape
+    if B <= 0 or L <= 0:
+        raise ValueError(f"snrse: {what} needs a non-empty batch, got [{B}, {L}]")
+    _dev(clean, noise)
+    if lengths is None:
+        lengths = np.full(B, L, np.int64)
+    return B, L, as_lengths(lengths, B, L, clean.device)
+
+
+def snr_window(fs):
+    """Samples of the 100-ms analysis window at `fs` Hz: int(fs * 0.1), as the definition writes it."""
+    W = int(fs * 0.1)
+    if W < 1:
+        raise ValueError(f"snrse: a sample rate of {fs} Hz leaves no 100-ms window")
+    return W
+
+
+def _snr_targets(snr_db, B, dev):
+    if torch.is_tensor(snr_db):
+        t = snr_db.to(device=dev, dtype=torch.float64).reshape(-1).contiguous()
+        if t.numel() != B:
+            raise ValueError(f"snrse: {t.numel()} snr_db targets for a batch of {B} rows")
+        return t
+    return torch.full((B,), float(snr_db), device=dev, dtype=torch.float64)
+
+
+def _active_analysis(clean, noise, ln, W, snr_db):
+    """-> (fin [B, 5] f64 = clean_rms, noise_rms, active windows, Pearson, gain; max |noise| [B] f32): the two
+    analysis launches, no read-back."""
+    B, L = clean.shape
+    dev = clean.device
+    nW = -(-L // W)
+    P = int(_lib.load().snrse_active_windows_per_block())
+    wsums = torch.empty(B, nW, 2, device=dev, dtype=torch.float64)
+    partials = torch.empty(B, -(-nW // P), 5, device=dev, dtype=torch.float64)
+    nmax = torch.empty(B, device=dev, dtype=torch.float32)
+    fin = torch.empty(B, 5, device=dev, dtype=torch.float64)
+    _lib.call("snrse_active_window_sums", clean.data_ptr(), noise.data_ptr(), ln.dev.data_ptr(), B, L, W,
+              wsums.data_ptr(), partials.data_ptr(), nmax.data_ptr(), _stream())
+    _lib.call("snrse_active_finalize", wsums.data_ptr(), partials.data_ptr(), nmax.data_ptr(), ln.dev.data_ptr(), B, L,
+              W, _snr_targets(snr_db, B, dev).data_ptr(), fin.data_ptr(), _stream())
+    return fin, nmax
+
+
+def _active_info(fin, nmax, ln, W):
+    return {"active_windows": fin[:, 2].to(torch.int64), "windows": torch.from_numpy(-(-ln.host // W)),
+            "corr": fin[:, 3], "gain": fin[:, 4], "max_noise": nmax}
+
+
+def active_rms(clean, noise, lengths=None, fs=16000, snr_db=-5.0, return_info=False):
+    """Active-level analysis of clean / noise pairs (the definition stands at snrse_active_window_sums in
+    include/snrse.h): [B, L] f32 on the device at `fs` Hz, row b valid on [0, L_b) (lengths None = whole rows) ->
+    [B, 2] f64 on the device, (clean_rms, noise_rms) over the 100-ms windows whose NOISE is active; both are eps
+    where no window is.  return_info: also a dict of device tensors: active_windows [B] int64, corr [B] f64 (the
+    Pearson coefficient of the whole rows), gain [B] f64 (what brings the pair to snr_db dB active SNR; snr_db a
+    scalar or a [B] tensor), max_noise [B] f32, and windows [B] int64 on the host.  Two launches, no read-back."""
+    B, L, ln = _snr_pair("active_rms", clean, noise, lengths)
+    W = snr_window(fs)
+    fin, nmax = _active_analysis(clean, noise, ln, W, snr_db)
+    rms = fin[:, :2].contiguous()
+    return (rms, _active_info(fin, nmax, ln, W)) if return_info else rms
+
+
+def snr_mix(clean, noise, gain, lengths=None):
+    """noise' = (float)gain_b noise and noisy = fma((float)gain_b, noise, clean) per row (snrse_snr_mix): [B, L] f32
+    batches and gain [B] f64, all on the device -> (noise', noisy [B, L] f32, zero past each length; max |noisy|
+    [B] f32)."""
+    B, L, ln = _snr_pair("snr_mix", clean, noise, lengths)
+    gain = gain.to(device=clean.device, dtype=torch.float64)
+    if gain.dim() != 1 or gain.numel() != B or gain.stride(0) < 1:
+        raise ValueError(f"snrse: snr_mix takes a [{B}] gain")
+    n1, y = torch.empty_like(clean), torch.empty_like(clean)
+    ymax = torch.empty(B, device=clean.device, dtype=torch.float32)
+    _lib.call("snrse_snr_mix", clean.data_ptr(), noise.data_ptr(), ln.dev.data_ptr(), B, L, gain.data_ptr(),
+              int(gain.stride(0)), n1.data_ptr(), y.data_ptr(), ymax.data_ptr(), _stream())
+    return n1, y, ymax
+
+
+def scale_to_pcm16(clean, noise, noisy, peak, lengths=None, floats=True, pcm16=True):
+    """The clip guard and the 16-bit conversion (snrse_scale_to_pcm16): three [B, L] f32 batches and peak [B] f32
+    (max |noisy| per row) on the device -> (floats, pcm, scale): scale [B] f64 = peak > 0.99 ? (0.99 - eps) / peak
+    : 1; floats = the three signals times (float)scale as new f32 tensors, pcm = those as int16 exactly as
+    audio.write_wav(bits=16) converts them; either is None when not asked for.  One launch, no read-back."""
+    B, L, ln = _snr_pair("scale_to_pcm16", clean, noise, lengths)
+    _dev(noisy, peak)
+    if noisy.shape != clean.shape or noisy.dtype != torch.float32 or peak.shape != (B,) or peak.dtype != torch.float32:
+        raise TypeError("snrse: scale_to_pcm16 takes three [B, L] float32 batches and a [B] float32 peak")
+    dev = clean.device
+    of = [torch.empty_like(clean) for _ in range(3)] if floats else [None] * 3
+    oq = [torch.empty(B, L, device=dev, dtype=torch.int16) for _ in range(3)] if pcm16 else [None] * 3
+    scale = torch.empty(B, device=dev, dtype=torch.float64)
+    _lib.call("snrse_scale_to_pcm16", clean.data_ptr(), noise.data_ptr(), noisy.data_ptr(), ln.dev.data_ptr(), B, L,
+              peak.data_ptr(), *[_ptr(t) for t in of], *[_ptr(t) for t in oq], scale.data_ptr(), _stream())
+    return (tuple(of) if floats else None), (tuple(oq) if pcm16 else None), scale
+
+
+def snr_remix(clean, noise, lengths=None, fs=16000, snr_db=-5.0, pcm16=False):
+    """Remix clean / noise pairs to snr_db dB active SNR (snr_db a scalar or a [B] tensor): the analysis of
+    active_rms, noise' = gain noise, noisy = clean + noise', and the clip guard (rows whose max |noisy| exceeds 0.99
+    have all three signals scaled to a peak of 0.99 - eps) -> (clean', noise', noisy, info), [B, L] on the device
+    and zero past each length: float32, or with pcm16 int16 as audio.write_wav(bits=16) would write those floats.
+    info: active_rms's dict plus rms [B, 2] f64 (of the INPUTS), peak [B] f32 (max |noisy| before the guard) and
+    scale [B] f64 (the guard's factor; the outputs' active RMS are rms[:, 0] scale and rms[:, 1] gain scale).
+    Four launches, no read-back."""
+    B, L, ln = _snr_pair("snr_remix", clean, noise, lengths)
+    W = snr_window(fs)
+    fin, nmax = _active_analysis(clean, noise, ln, W, snr_db)
+    n1, y, peak = snr_mix(clean, noise, fin[:, 4], lengths=ln)
+    of, oq, scale = scale_to_pcm16(clean, n1, y, peak, lengths=ln, floats=not pcm16, pcm16=pcm16)
+    info = _active_info(fin, nmax, ln, W)
+    info.update(rms=fin[:, :2].contiguous(), peak=peak, scale=scale)
+    return (*(oq if pcm16 else of), info)
+
+
 def range_stats(t, peak=None, nonfinite=None, accumulate=False):
     """Range statistics of a contiguous device tensor whose leading dimension counts the rows (float32, float16,
     bfloat16, or complex64 read as interleaved floats): (peak [B] f32 = max |v| over the finite elements of each
