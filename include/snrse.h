@@ -306,6 +306,47 @@ int snrse_resample_poly(const float* x, const int* lengths, int B, long long str
                         const float* taps, float* y, long long stride_out, hipStream_t stream);
 int snrse_resample_poly_block(void);
 
+/* The band above 8 kHz, kept at the recording's own rate (csrc/highband.hip).  The networks run at 16 kHz, so a
+ * recording at R > 16000 comes back from them band-limited.  For one row let y be the recording at rate R (L
+ * samples), u its 16 kHz version (L16 = ceil(L 16000 / R) samples, what the enhancers consume), x the enhanced
+ * 16 kHz row (L16 samples), h the 16 k -> R filter in the resampler's phase-major layout with up / down = R / 16000
+ * in lowest terms, and U(v)[n] = sum_j v[j] h[n down + half - j up], 0 <= n < L, the arithmetic above.  Then
+ *   out[n] = U(x)[n] + g[n] (y[n] - U(u)[n]) = g[n] y[n] + sum_j h[.] (x[j] - g[n] u[j]).
+ * y = U(u) + (y - U(u)) holds by construction: g = 1 with x = u returns y, g = 0 is the plain resampler, and
+ * g < 1 blends the anti-alias filter's crossover smoothly instead of leaving a hole.
+ *
+ * The gain g[n]: a constant (gains NULL: gain_const), or linear interpolation between per-frame values g_s, frame
+ * t centred at 16 kHz sample 128 t, in integer arithmetic: num = n 16000, den = R 128 (64-bit; n down and up 128
+ * after the reduction, the same quotient and the same fraction), i = num / den, a = (num % den) / den,
+ *   g[n] = (1 - a) g_s[min(i, T - 1)] + a g_s[min(i + 1, T - 1)],
+ * exactly g_s[i] where den divides num.  gains [B][Tmax] f32 with frames [B] int32 (T_b, 1 <= T_b <= Tmax; T_b < 1
+ * counts as g = 0), values >= 0; nothing at or past T_b of a row is read.
+ *
+ * snrse_resample_mix: x, u [B][stride16] f32 with len16 [B], y [B][strideR] f32 with lenR [B] -> out [B][strideR]
+ * f32, all on the device.  One output per thread, the block's span of x and u staged in LDS with zeros outside
+ * [0, L16_b); nothing at or past a row's length is read in any input, outputs [L_b, strideR) are written as zero.
+ * One fp32 fma chain over j ascending per output: no atomics, the same bits on every launch and for a row launched
+ * alone.  up > down, coprime; the definition covers L_b <= ceil(L16_b up / down), a recording no longer than its
+ * 16 kHz version brought back up (snrse.ops.resample_mix refuses a longer one; past that length U is zero).
+ * EINVAL when the staged span of x and u exceeds 64 KB of LDS.
+ *
+ * snrse_band_gain: the "follow" policy's g_s -- the high band is attenuated as much as the network attenuated the
+ * top octave it saw.  With S the raw STFT (n_fft 510, hop 128, periodic Hann, centred, reflect at the row's own
+ * L16, un-normalised) and T_b = 1 + L16_b / 128 frames:
+ *   E_u[t], E_x[t] = sum over bins k = 128 .. 255 of |S[k, t]|^2 of u and of x,
+ *   g_f[t] = 1 where E_u[t] == 0, else clamp(sqrt(E_x[t] / E_u[t]), floor_gain, 1), floor_gain = 10^(-floor_db / 20),
+ *   g_s[t] = the mean of g_f over frames max(0, t - 2) .. min(T_b - 1, t + 2) (truncated, not zero-padded).
+ * u, x [B][Lstride] f32 with lengths [B] int32 (the CALLER checks 255 < L_b <= Lstride and T_b <= Tmax);
+ * energies: a workspace of B * 2 * Tmax doubles (E_u, E_x per row); gains [B][Tmax] f32, zero from T_b on.  The
+ * DFT, the energies and the ratios are fp64 in a fixed order, the result is rounded to fp32 once; two launches on
+ * the stream, no host synchronisation. */
+int snrse_resample_mix(const float* x, const float* u, const int* len16, long long stride16, const float* y,
+                       const int* lenR, long long strideR, int B, int up, int down, int half, const float* taps,
+                       const float* gains, const int* frames, int Tmax, float gain_const, float* out,
+                       hipStream_t stream);
+int snrse_band_gain(const float* u, const float* x, const int* lengths, int B, int Lstride, int Tmax,
+                    double floor_gain, double* energies, float* gains, hipStream_t stream);
+
 /* Recordings of any length (csrc/window.hip, snrse/longform.py): a recording is cut into overlapping windows of W
  * samples, the windows run as rows of the batched enhancers, and their results are joined by a cross-fade over the
  * first V samples of every window of a recording but its first.

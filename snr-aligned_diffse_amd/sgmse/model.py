@@ -408,7 +408,7 @@ class ScoreModel(nn.Module):
     def enhance_batch(self, ys, seeds=None, batch_size=32, max_frames=16384, sampler_type="pc",
                       predictor="reverse_diffusion", corrector="ald", N=30, corrector_steps=1, snr=0.5, oracle=False,
                       clean_rms=None, noise_rms=None, range_guard="auto", sample_rates=None, output_rate="model",
-                      window_frames=None, overlap_frames=64, **kwargs):
+                      window_frames=None, overlap_frames=64, highband="drop", highband_floor_db=30.0, **kwargs):
         """enhance() for a list of noisy utterances of different lengths (each [L], [1, L], numpy or tensor) ->
         list of numpy [L_i] in input order.  Utterances whose spectrograms pad to the same frame count share a
         ragged batch (snrse.batching.plan_batches: at most batch_size rows and max_frames frames per batch).
@@ -446,13 +446,27 @@ class ScoreModel(nn.Module):
         batch_size rows or max_frames frames, so device memory does not grow with the recording beyond about three
         copies of its samples.  A window of digital silence (max|y| = 0) is not sent to the network and counts as
         zeros.  last_guard["flagged"] lists utterances as before, last_guard["flagged_windows"] the
-        (utterance, window) pairs."""
+        (utterance, window) pairs.
+
+        highband (with sample_rates and output_rate="input" only; anything else but "drop" raises before any device
+        work): what becomes of the band above 8 kHz of a recording at more than 16 kHz, which the networks never
+        see.  "drop" (the default) resamples the result back as before, bit for bit.  "keep" adds the recording's
+        own band back unchanged, a float adds it at that gain in dB (<= 0), and "follow" attenuates it frame by
+        frame as much as the network attenuated the top octave it saw (4 - 8 kHz), by at most highband_floor_db dB
+        (snrse.resample.restore_highband: out = U(x) + g (y - U(u)), one ops.resample_mix launch per distinct
+        rate; include/snrse.h has the definition).  It costs two more copies of the call's recordings at their
+        own rates on the device while the results are mixed.  Recordings at 16 kHz or below are not affected."""
         from snrse import batching
+        hb = "drop"
+        if not (isinstance(highband, str) and highband == "drop"):  # the default stays clear of snrse.resample
+            from snrse import resample as _rs
+            hb = _rs.check_highband(highband, highband_floor_db, sample_rates, output_rate)
         if window_frames is not None:
             return self._enhance_windowed(ys, seeds, batch_size, max_frames, sample_rates, output_rate,
                                           window_frames, overlap_frames, oracle, clean_rms, noise_rms, range_guard,
                                           dict(sampler_type=sampler_type, predictor=predictor, corrector=corrector,
-                                               N=N, corrector_steps=corrector_steps, snr=snr), kwargs)
+                                               N=N, corrector_steps=corrector_steps, snr=snr), kwargs,
+                                          hb, highband_floor_db)
         n = len(ys)
         route = self._batch_route(sampler_type, corrector, kwargs)
         if sample_rates is not None:
@@ -464,13 +478,17 @@ class ScoreModel(nn.Module):
             if seeds is None and route is not None:
                 seeds = [_samp.draw_seed() for _ in range(n)]
             lens_in = [int(resample.as_signal(y).numel()) for y in ys]
+            if hb == "follow":
+                resample.check_follow_lengths(lens_in, sample_rates)
             # the batched enhancers gather their ragged batches on the device, where the resampled rows already are
             ys16 = resample.convert(ys, sample_rates, audio.MODEL_RATE, on_device=route is not None)
             out = self.enhance_batch(ys16, seeds=seeds, batch_size=batch_size, max_frames=max_frames,
                                      sampler_type=sampler_type, predictor=predictor, corrector=corrector, N=N,
                                      corrector_steps=corrector_steps, snr=snr, oracle=oracle, clean_rms=clean_rms,
                                      noise_rms=noise_rms, range_guard=range_guard, **kwargs)
-            if output_rate == "input":
+            if output_rate == "input" and hb != "drop":  # the ys16 of above serve as the band split's 16 kHz side
+                out = resample.restore_highband(out, ys16, ys, sample_rates, hb, highband_floor_db)
+            elif output_rate == "input":
                 back = resample.convert(out, audio.MODEL_RATE, sample_rates)
                 out = [np.asarray(h)[:L] for h, L in zip(back, lens_in)]
             return out
@@ -522,7 +540,8 @@ class ScoreModel(nn.Module):
         return out
 
     def _enhance_windowed(self, ys, seeds, batch_size, max_frames, sample_rates, output_rate, window_frames,
-                          overlap_frames, oracle, clean_rms, noise_rms, range_guard, skw, kwargs):
+                          overlap_frames, oracle, clean_rms, noise_rms, range_guard, skw, kwargs, highband="drop",
+                          highband_floor_db=30.0):
         """enhance_batch(window_frames=...): plan (snrse.longform) -> one gather -> the windows through the route's
         enhancer, batch by batch, their results written back over the windows -> one merge.  skw: the sampler
         keywords of enhance()."""
@@ -546,6 +565,8 @@ class ScoreModel(nn.Module):
             return []
         sigs = [resample.as_signal(y) for y in ys]
         lens_in = [int(s.numel()) for s in sigs]
+        if highband == "follow":
+            resample.check_follow_lengths(lens_in, sample_rates)
         if sample_rates is not None:
             sigs = resample.convert(sigs, sample_rates, audio.MODEL_RATE, on_device=True)
         lens = [int(s.numel()) for s in sigs]
@@ -558,6 +579,7 @@ class ScoreModel(nn.Module):
         # the recordings go up once; every window is cut on the device, and the enhancers' results overwrite it
         src = sigs[0].reshape(1, -1) if n == 1 else batching.pack_rows(sigs)[0]  # one recording needs no packing
         wins = ops.window_gather(src.to(dev).contiguous(), lens, plan.table, W)
+        noisy16 = sigs if highband != "drop" else None  # the band split's 16 kHz side: kept until the merge
         del sigs, src
         wl = np.asarray(plan.win_lengths, np.int64)
         silent = ops.absmax(wins, lengths=wl).cpu().numpy() == 0  # the call's one read-back before the results
@@ -603,7 +625,9 @@ class ScoreModel(nn.Module):
         self.last_guard = dict(guard, flagged=sorted({u for u, _ in flagged}), flagged_windows=sorted(flagged))
         self.last_windows = plan.counts()
         out = [out[r, :lens[r]].copy() for r in range(n)]
-        if sample_rates is not None and output_rate == "input":
+        if sample_rates is not None and output_rate == "input" and highband != "drop":
+            out = resample.restore_highband(out, noisy16, ys, sample_rates, highband, highband_floor_db)
+        elif sample_rates is not None and output_rate == "input":
             back = resample.convert(out, audio.MODEL_RATE, sample_rates)
             out = [np.asarray(h)[:L] for h, L in zip(back, lens_in)]
         return out

@@ -48,6 +48,8 @@ SIGNATURES = {
     "snrse_absmax": [_vp, _i, _i, _vp, _vp],
     "snrse_range_stats": [_vp, _i, _ll, _i, _vp, _vp, _i, _vp],
     "snrse_resample_poly": [_vp, _vp, _i, _ll, _i, _i, _i, _vp, _vp, _ll, _vp],
+    "snrse_resample_mix": [_vp, _vp, _vp, _ll, _vp, _vp, _ll, _i, _i, _i, _i, _vp, _vp, _vp, _i, _f, _vp, _vp],
+    "snrse_band_gain": [_vp, _vp, _vp, _i, _i, _i, _d, _vp, _vp, _vp],
     "snrse_window_gather": [_vp, _vp, _i, _ll, _vp, _i, _i, _vp, _vp],
     "snrse_window_merge": [_vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _ll, _vp],
     "snrse_energy_ratios": [_vp, _vp, _vp, _i, _i, _vp, _vp],

@@ -32,6 +32,8 @@ FILE_FLAGS["ode.hip"] = ["-ffp-contract=off"]
 FILE_FLAGS["window.hip"] = ["-ffp-contract=off"]
 # The remix of snrize.hip is two written-out expressions (g n and fma(g, n, c)) whose error bound counts their roundings
 FILE_FLAGS["snrize.hip"] = ["-ffp-contract=off"]
+# The high-band mix of highband.hip is written-out fmas (gain interpolation, difference, chain) whose bound counts their roundings
+FILE_FLAGS["highband.hip"] = ["-ffp-contract=off"]
 
 
 def _sources(csrc=CSRC):

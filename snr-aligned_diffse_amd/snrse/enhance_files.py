@@ -25,7 +25,13 @@ ranks (snrse.dist.shard_range); rank 0 writes the csv, which needs the headers o
 
     python -m snrse.enhance_files --noisy_dir DIR --ckpt CKPT --destination_folder OUT \\
         [--batch_size 32] [--output_rate model|input] [--seed S] [--N 30 --sampler_type pc ...] \\
-        [--window_frames 512 [--overlap_frames 64]]
+        [--window_frames 512 [--overlap_frames 64]] \\
+        [--highband drop|keep|follow | --highband_gain_db X] [--highband_floor_db 30]
+
+--highband (with --output_rate input) says what becomes of the band above 8 kHz of a file at more than 16 kHz, which
+the 16 kHz networks never see: drop (the default) writes the networks' band alone, as before; keep adds the file's own
+band back unchanged, --highband_gain_db X adds it at X dB (<= 0), and follow attenuates it frame by frame as much as
+the network attenuated the top octave it saw, by at most --highband_floor_db dB (ScoreModel.enhance_batch(highband=...)).
 """
 from __future__ import annotations
 
@@ -38,7 +44,7 @@ from os.path import join
 import numpy as np
 import torch
 
-from . import audio, dist as sdist, longform
+from . import audio, dist as sdist, longform, resample
 from .batching import plan_batches
 from .evaluate import load_model, reverse_start, sampler_arguments, sampler_kwargs
 from .sampler import draw_seed
@@ -85,11 +91,13 @@ def enhance_files(model, noisy_dir, target_dir, batch_size=32, max_frames=16384,
                   world=1, sampler_type="pc", predictor="reverse_diffusion", corrector="ald", corrector_steps=1,
                   snr=0.5, N=30, reverse_starting_point=1.0, force_N=0, atol=1e-5, rtol=1e-5,
                   timestep_type="linear", correct_stepsize=False, window_frames=None, overlap_frames=64,
-                  **enhance_kw):
+                  highband="drop", highband_floor_db=30.0, **enhance_kw):
     """-> the list_files() rows of every file (all ranks'); this rank's share is enhanced and written.
-    window_frames / overlap_frames: ScoreModel.enhance_batch's (None: every channel is one network input)."""
+    window_frames / overlap_frames: ScoreModel.enhance_batch's (None: every channel is one network input), and so
+    are highband / highband_floor_db (anything but "drop" needs output_rate="input")."""
     if output_rate not in ("model", "input"):
         raise ValueError(f"enhance_files: output_rate is 'model' or 'input', got {output_rate!r}")
+    highband = resample.check_highband(highband, highband_floor_db, (), output_rate)
     window = None
     if window_frames is not None:
         longform.geometry(window_frames, overlap_frames)
@@ -107,6 +115,8 @@ def enhance_files(model, noisy_dir, target_dir, batch_size=32, max_frames=16384,
     seeds = draw_seeds(len(utts)) if model._batch_route(sampler_type, corrector, enhance_kw) is not None else None
     if window:  # the calls are planned as without it, by the channels' whole lengths; the windows inside each call
         kw.update(window_frames=window_frames, overlap_frames=overlap_frames)
+    if highband != "drop":
+        kw.update(highband=highband, highband_floor_db=highband_floor_db)
     lens = [audio.resampled_length(mine[k][1], mine[k][3], audio.MODEL_RATE) for k, _ in utts]
     done = {k: [None] * f[2] for k, f in enumerate(mine)}
     for batch in plan_batches(lens, batch_size, max_frames):
@@ -147,8 +157,21 @@ def parser():
                          "= 8.2 s is the flagship shape); off by default")
     ap.add_argument("--overlap_frames", type=int, default=64,
                     help="frames over which neighbouring windows are cross-faded (with --window_frames)")
+    hb = ap.add_mutually_exclusive_group()
+    hb.add_argument("--highband", type=str, choices=resample.HIGHBAND_POLICIES, default="drop",
+                    help="the band above 8 kHz of files at more than 16 kHz (with --output_rate input): drop it (as "
+                         "before), keep it, or let it follow the network's attenuation of the top octave it saw")
+    hb.add_argument("--highband_gain_db", type=float, default=None,
+                    help="keep that band at this fixed gain in dB (<= 0) instead")
+    ap.add_argument("--highband_floor_db", type=float, default=30.0,
+                    help="the most --highband follow attenuates the band, in dB")
     sampler_arguments(ap)
     return ap
+
+
+def highband_argument(a):
+    """The parsed --highband / --highband_gain_db pair -> enhance_batch's highband."""
+    return a.highband if a.highband_gain_db is None else float(a.highband_gain_db)
 
 
 def main(argv=None):
@@ -159,7 +182,7 @@ def main(argv=None):
         torch.manual_seed(a.seed)
     enhance_files(model, a.noisy_dir, a.destination_folder, batch_size=a.batch_size, output_rate=a.output_rate,
                   rank=rank, world=world, window_frames=a.window_frames, overlap_frames=a.overlap_frames,
-                  **sampler_kwargs(a))
+                  highband=highband_argument(a), highband_floor_db=a.highband_floor_db, **sampler_kwargs(a))
 
 
 if __name__ == "__main__":

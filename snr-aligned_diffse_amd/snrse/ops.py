@@ -777,6 +777,87 @@ def resample_poly(x, up, down, lengths=None, taps=None):
     return y, out_dev
 
 
+def _host_lengths(what, lengths, B, lo, hi):
+    host = np.asarray(lengths.cpu() if torch.is_tensor(lengths) else lengths).astype(np.int64).reshape(-1)
+    if len(host) != B or (host < lo).any() or (host > hi).any():
+        raise ValueError(f"snrse: {what} needs {B} lengths inside [{lo}, {hi}]")
+    return host
+
+
+def band_gain(u, x, lengths, floor_db=30.0):
+    """The "follow" policy's gain frames (snrse_band_gain; the definition stands in include/snrse.h): u the 16 kHz
+    rows the network saw, x its results, [B, stride] f32 on the device, row b valid on [0, L_b), 256 <= L_b <=
+    stride -> (g_s [B, Tmax] f32, frames [B] int32), both on the device, T_b = 1 + L_b // 128 and Tmax their
+    maximum; g_s is zero from T_b on.  floor_db >= 0: the most the band is attenuated.  No read-back."""
+    _dev(u, x)
+    if u.dim() != 2 or u.dtype != torch.float32 or x.dtype != torch.float32 or u.shape != x.shape:
+        raise TypeError("snrse: band_gain takes two [B, L] float32 batches of one shape")
+    B, stride = u.shape
+    floor_db = float(floor_db)
+    if not (floor_db >= 0.0) or not math.isfinite(floor_db):
+        raise ValueError(f"snrse: band_gain needs a finite floor_db >= 0, got {floor_db}")
+    host = _host_lengths("band_gain (the STFT's reflect padding)", lengths, B, 256, stride)
+    frames = 1 + host // 128
+    Tmax = int(frames.max())
+    ln = torch.from_numpy(host.astype(np.int32)).to(u.device)
+    energies = torch.empty(B, 2, Tmax, device=u.device, dtype=torch.float64)
+    gains = torch.empty(B, Tmax, device=u.device, dtype=torch.float32)
+    _lib.call("snrse_band_gain", u.data_ptr(), x.data_ptr(), ln.data_ptr(), B, stride, Tmax,
+              10.0 ** (-floor_db / 20.0), energies.data_ptr(), gains.data_ptr(), _stream())
+    return gains, torch.from_numpy(frames.astype(np.int32)).to(u.device)
+
+
+def resample_mix(x, u, y, len16, lenR, rate, gain, frames=None):
+    """The enhanced 16 kHz rows brought to `rate` > 16000 with the band above 8 kHz of the recordings mixed back in
+    (snrse_resample_mix; the definition stands in include/snrse.h): out = U(x) + g (y - U(u)).  x, u [B, stride16]
+    f32 with len16 [B]; y [B, strideR] f32 with lenR [B] (lenR_b <= ceil(len16_b rate / 16000): a recording is no
+    longer than its 16 kHz version brought back up), all on the device; gain: a constant in [0, 1], or the
+    frames [B, Tmax] f32 on the device that band_gain returns, with frames [B] (None: 1 + len16 // 128) -> out
+    [B, strideR] f32, zero from lenR_b on.  The project's default 16 k -> rate filter.  One launch, no read-back."""
+    _dev(x, u, y)
+    for t in (x, u, y):
+        if t.dim() != 2 or t.dtype != torch.float32:
+            raise TypeError("snrse: resample_mix takes [B, L] float32 batches")
+    if x.shape != u.shape or y.shape[0] != x.shape[0]:
+        raise ValueError(f"snrse: resample_mix takes x, u of one shape and y of as many rows, got {tuple(x.shape)}, "
+                         f"{tuple(u.shape)}, {tuple(y.shape)}")
+    from .audio import MODEL_RATE, rational, resample_taps
+    B, s16 = x.shape
+    sR = y.shape[1]
+    rate = int(rate)
+    if rate <= MODEL_RATE:
+        raise ValueError(f"snrse: resample_mix keeps the band above {MODEL_RATE // 2} Hz of rates above {MODEL_RATE}, "
+                         f"got {rate}")
+    if B <= 0 or s16 <= 0 or sR <= 0:
+        raise ValueError("snrse: resample_mix needs rows and samples")
+    h16 = _host_lengths("resample_mix (len16)", len16, B, 0, s16)
+    hR = _host_lengths("resample_mix (lenR)", lenR, B, 0, sR)
+    up, down = rational(MODEL_RATE, rate)
+    bad = [int(i) for i in np.nonzero(hR > -((-h16 * up) // down))[0]]
+    if bad:
+        raise ValueError(f"snrse: resample_mix rows {bad} are longer at {rate} Hz than their 16 kHz signals brought "
+                         f"back up (lenR <= ceil(len16 {up} / {down}))")
+    tp, half = cached_taps(resample_taps, up, down, x.device)
+    gp, fp, Tmax, gc = None, None, 0, 0.0
+    if torch.is_tensor(gain):
+        _dev(gain)
+        if gain.dim() != 2 or gain.dtype != torch.float32 or gain.shape[0] != B or gain.shape[1] < 1:
+            raise ValueError(f"snrse: resample_mix takes gain frames [B, Tmax] float32, got {tuple(gain.shape)}")
+        gp, Tmax = gain, gain.shape[1]
+        fh = _host_lengths("resample_mix (frames)", 1 + h16 // 128 if frames is None else frames, B, 1, Tmax)
+        fp = torch.from_numpy(fh.astype(np.int32)).to(x.device)
+    else:
+        gc = float(gain)
+        if not 0.0 <= gc <= 1.0:
+            raise ValueError(f"snrse: resample_mix takes a constant gain inside [0, 1], got {gain}")
+    l16 = torch.from_numpy(h16.astype(np.int32)).to(x.device)
+    lR = torch.from_numpy(hR.astype(np.int32)).to(x.device)
+    out = torch.empty(B, sR, device=x.device, dtype=torch.float32)
+    _lib.call("snrse_resample_mix", x.data_ptr(), u.data_ptr(), l16.data_ptr(), s16, y.data_ptr(), lR.data_ptr(), sR,
+              B, up, down, half, tp.data_ptr(), _ptr(gp), _ptr(fp), Tmax, gc, out.data_ptr(), _stream())
+    return out
+
+
 def _i32(v, dev, shape=None):
     """A table of integers (sequence / numpy, or an int32 tensor already on `dev`) -> contiguous int32 on `dev`."""
     if torch.is_tensor(v) and v.dtype == torch.int32 and v.device == dev:
