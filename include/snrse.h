@@ -404,6 +404,72 @@ int snrse_estoi(const float* x, const float* y, const int* lengths, int B, long 
 size_t snrse_estoi_workspace(int B, long long stride);
 int snrse_estoi_block(void);
 
+/* Programme loudness, ITU-R BS.1770-4 integrated loudness of ragged batches (csrc/loudness.hip, snrse/loudness.py).
+ *
+ * K-weighting for a sample rate fs: the standard's analog prototype re-discretised per rate (at 48 kHz the
+ * standard's table to 1e-13).  With K = tan(pi f0 / fs) and a0 = 1 + K / Q + K^2:
+ *   shelf      f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196,
+ *              Vh = 10^(G / 20), Vb = Vh^0.4996667741545416,
+ *              b = [(Vh + Vb K / Q + K^2) / a0, 2 (K^2 - Vh) / a0, (Vh - Vb K / Q + K^2) / a0]
+ *              a = [1, 2 (K^2 - 1) / a0, (1 - K / Q + K^2) / a0]
+ *   high-pass  f0 = 38.13547087602444, Q = 0.5003270373238773,
+ *              b = [1, -2, 1], a = [1, 2 (K^2 - 1) / a0, (1 - K / Q + K^2) / a0]
+ * computed by the host in float64 (snrse.loudness.kweighting) and handed over as doubles.  z = HP(shelf(x)), both
+ * biquads in transposed direct form II from a zero state; the samples are read as f32, everything after is f64.
+ *
+ * Blocks.  n100 = (fs + 5) / 10 samples (integer division).  Sub-block i of a row of length L is
+ * s_i = sum of z[n]^2 over n in [i n100, (i + 1) n100), for i < nsub = L / n100; the tail of fewer than n100 samples
+ * is not used.  Block j of a FILE (a set of rows: its channels) is
+ *   e_j = sum over its rows of (s_j + s_{j+1} + s_{j+2} + s_{j+3}) / (4 n100),   j <= nsub - 4,
+ * 400 ms at a hop of 100 ms, every channel with weight 1 (the files carry no channel layout; the standard's 1.41 for
+ * surround channels is not applied).  l_j = -0.691 + 10 log10(e_j).
+ * Gates.  Keep j with l_j > -70; Gamma = -0.691 + 10 log10(mean of e_j over the kept) - 10; the integrated loudness
+ * I = -0.691 + 10 log10(mean of e_j over the kept with l_j > Gamma).  No block (nsub < 4) or none kept: I = -inf.
+ *
+ * snrse_kweight_sums: x [B][stride] f32 with lengths [B] int32 on the device; params [B][42] f64 per row = the ten
+ * coefficients (shelf b0 b1 b2 a1 a2, high-pass b0 b1 b2 a1 a2), then A^C and A^(C S) row-major 4 x 4, A the
+ * zero-input transition of one sample on the state (shelf w1, w2, high-pass w1, w2), C = snrse_kweight_chunk()
+ * and S = snrse_kweight_group(); n100 [B] int32 (rows of different rates share the launches; a row with
+ * n100 < C has no sub-block) -> sums [B][Nmax] f64, s_i for i < min(nsub_b, Nmax) and 0 from there on.  A row is cut
+ * into chunks of C samples: every chunk's zero-state final state, a scan s_{k+1} = A^C s_k + f_k over the row in
+ * groups of S chunks, then every chunk again from its exact state -- the recurrence's own values, no run-in -- with
+ * z^2 summed into the (at most two) sub-blocks it touches; one wave per sub-block adds the chunks' partials in a
+ * fixed order.  The filtered signal is never stored.  snrse_kweight_block() chunks share a workgroup, which stages
+ * their samples in LDS.  No floating-point atomics: a row's bits do not depend on the batch, the row's place in
+ * it or the launch.  Nothing at or past L_b is read; L_b = 0 is allowed.  work: snrse_kweight_workspace(B, stride)
+ * bytes of device memory, 256-byte aligned (0, no valid size, for B <= 0, stride <= 0 or stride >= 2^31).  Six
+ * launches, no host synchronisation.  EINVAL before any HIP call for a NULL pointer, a size <= 0, x not 4-byte
+ * aligned or a short workspace.
+ *
+ * snrse_loudness_gate: sums [B][Nmax], nsub [B] (clamped to [0, Nmax]), n100 [B], group [B] int32 = the file of
+ * each row, in [0, G); the rows of a file are adjacent and share one rate, a file has the fewest sub-blocks of its
+ * rows -> per file lufs [G] f64 = I, counts [G][3] int32 = blocks, blocks kept by the absolute gate, blocks kept by
+ * the relative gate, margin [G] f64 = the smallest |l_j - gate| in LU over every comparison made (l_j with -70, and
+ * the blocks above -70 with Gamma; +inf when no comparison was made), which shows a decision that rested on
+ * rounding.  One workgroup per file, fp64, sums in a fixed order, no host synchronisation.
+ *
+ * snrse_peak_oversampled: out [B] f32 = max |y[m]| over m in [0, up L_b) of y = snrse_resample_poly(x, up, down = 1)
+ * with the same taps layout ([up][K]) and the same fp32 fma chain over j ascending, so the value has the bits of the
+ * maximum of that entry's output, which is never written here; 0 for L_b = 0.  A NaN output is skipped, by
+ * snrse_absmax's rule.  The host calls it with up = 4 and the resampler's default 81-tap filter: a 4x oversampled
+ * peak, NOT the 48-tap filter of BS.1770 Annex 2, hence no "dBTP".
+ *
+ * snrse_gain_to_pcm16: q [B][stride] int16 = clip(rint(fl32(fl32(gain[b]) x) 32768), -32768, 32767), rint to even:
+ * what a 16-bit wav writer makes of the f32 product; f (may be NULL) [B][stride] f32 = that product.  gain [B] f64
+ * on the device; both outputs are zero from L_b on. */
+int snrse_kweight_sums(const float* x, const int* lengths, int B, long long stride, const double* params,
+                       const int* n100, void* work, size_t work_bytes, double* sums, int Nmax, hipStream_t stream);
+size_t snrse_kweight_workspace(int B, long long stride);
+int snrse_kweight_chunk(void);
+int snrse_kweight_block(void);
+int snrse_kweight_group(void);
+int snrse_loudness_gate(const double* sums, int Nmax, const int* nsub, const int* n100, const int* group, int B, int G,
+                        double* lufs, int* counts, double* margin, hipStream_t stream);
+int snrse_peak_oversampled(const float* x, const int* lengths, int B, long long stride, int up, int half,
+                           const float* taps, float* out, hipStream_t stream);
+int snrse_gain_to_pcm16(const float* x, const int* lengths, int B, long long stride, const double* gain, short* q,
+                        float* f, hipStream_t stream);
+
 /* Range statistics of a contiguous tensor [B][per] (dtype SNRSE_F32 / SNRSE_F16 / SNRSE_BF16; a complex64
  * spectrogram is 2*per floats): peak[b] = max |v| over the FINITE elements of row b (0 when there is none),
  * nonfinite[b] = number of inf / NaN elements of row b (saturating at INT_MAX).  accumulate == 0: overwrite

@@ -102,6 +102,11 @@ SIGNATURES = {
     "snrse_active_finalize": [_vp, _vp, _vp, _vp, _i, _ll, _i, _vp, _vp, _vp],
     "snrse_snr_mix": [_vp, _vp, _vp, _i, _ll, _vp, _i, _vp, _vp, _vp, _vp],
     "snrse_scale_to_pcm16": [_vp, _vp, _vp, _vp, _i, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    # programme loudness (csrc/loudness.hip)
+    "snrse_kweight_sums": [_vp, _vp, _i, _ll, _vp, _vp, _vp, C.c_size_t, _vp, _i, _vp],
+    "snrse_loudness_gate": [_vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp],
+    "snrse_peak_oversampled": [_vp, _vp, _i, _ll, _i, _i, _vp, _vp, _vp],
+    "snrse_gain_to_pcm16": [_vp, _vp, _i, _ll, _vp, _vp, _vp, _vp],
 }
 HOUSEKEEPING = {"snrse_abi_version": ([], _i), "snrse_build_id": ([], C.c_char_p), "snrse_error_string": ([_i], C.c_char_p),
                 "snrse_device_name": ([C.c_char_p, _i], _i), "snrse_snrnet_workspace": ([_i, _i], C.c_size_t),
@@ -109,6 +114,8 @@ HOUSEKEEPING = {"snrse_abi_version": ([], _i), "snrse_build_id": ([], C.c_char_p
                 "snrse_rk45_rownorm_blocks": ([_i, _ll], _i), "snrse_resample_poly_block": ([], _i),
                 "snrse_estoi_workspace": ([_i, _ll], C.c_size_t), "snrse_estoi_block": ([], _i),
                 "snrse_active_windows_per_block": ([], _i),
+                "snrse_kweight_workspace": ([_i, _ll], C.c_size_t), "snrse_kweight_chunk": ([], _i),
+                "snrse_kweight_block": ([], _i), "snrse_kweight_group": ([], _i),
                 "snrse_ctx_create": ([], _vp), "snrse_ctx_destroy": ([_vp], None)}
 
 _lib = None

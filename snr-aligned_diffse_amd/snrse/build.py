@@ -34,6 +34,9 @@ FILE_FLAGS["window.hip"] = ["-ffp-contract=off"]
 FILE_FLAGS["snrize.hip"] = ["-ffp-contract=off"]
 # The high-band mix of highband.hip is written-out fmas (gain interpolation, difference, chain) whose bound counts their roundings
 FILE_FLAGS["highband.hip"] = ["-ffp-contract=off"]
+# The K-weighting recurrence of loudness.hip must give the same bits from a chunk's zero state and from its carried state,
+# and its gain-to-PCM product rounds once before the scale by 32768: written-out operations, no contraction
+FILE_FLAGS["loudness.hip"] = ["-ffp-contract=off"]
 
 
 def _sources(csrc=CSRC):

@@ -26,12 +26,25 @@ ranks (snrse.dist.shard_range); rank 0 writes the csv, which needs the headers o
     python -m snrse.enhance_files --noisy_dir DIR --ckpt CKPT --destination_folder OUT \\
         [--batch_size 32] [--output_rate model|input] [--seed S] [--N 30 --sampler_type pc ...] \\
         [--window_frames 512 [--overlap_frames 64]] \\
-        [--highband drop|keep|follow | --highband_gain_db X] [--highband_floor_db 30]
+        [--highband drop|keep|follow | --highband_gain_db X] [--highband_floor_db 30] \\
+        [--loudness off|input|LUFS [--peak_db -1.0]]
 
 --highband (with --output_rate input) says what becomes of the band above 8 kHz of a file at more than 16 kHz, which
 the 16 kHz networks never see: drop (the default) writes the networks' band alone, as before; keep adds the file's own
 band back unchanged, --highband_gain_db X adds it at X dB (<= 0), and follow attenuates it frame by frame as much as
 the network attenuated the top octave it saw, by at most --highband_floor_db dB (ScoreModel.enhance_batch(highband=...)).
+
+--loudness (off by default) sets the level of the written files, which otherwise is whatever the noisy peak made it:
+a number brings every file to that integrated loudness in LUFS (ITU-R BS.1770-4 as snrse.loudness states it: -23 is
+EBU R 128, podcasts use -16 .. -19), `input` gives it the integrated loudness of the noisy file it came from, measured
+at that file's own rate.  Once all channels of a file are done they are measured together on the device at the rate
+they are written at, ONE gain is applied to all of them (the stereo image is kept) and the 16-bit samples come from
+the device conversion (ops.gain_to_pcm16).  --peak_db X (default -1, at most 0) is a ceiling on the 4x-oversampled
+peak: where the gain would pass it the gain is reduced to meet it -- a plain gain reduction, no limiter -- and the file
+is marked `limited`.  A file with no 400-ms block above -70 LUFS (silence, or shorter than 400 ms) is written with
+gain 1.  _enhanced.csv then ends with the columns input_lufs (the noisy file), enhanced_lufs (the enhanced file before
+the gain), gain_db, peak_db (the 4x peak after the gain) and limited (0 / 1); written loudness = enhanced_lufs +
+gain_db.  It works with every --output_rate, --window_frames and --highband setting.
 """
 from __future__ import annotations
 
@@ -74,30 +87,68 @@ def draw_seeds(n):
     return [draw_seed() for _ in range(n)]
 
 
-def write_csv(files, output_rate, target_dir, window=None):
-    """window: None, or (window_frames, overlap_frames): one more column, the windows of each channel."""
+LOUDNESS_COLUMNS = ("input_lufs", "enhanced_lufs", "gain_db", "peak_db", "limited")
+
+
+def write_csv(files, output_rate, target_dir, window=None, loud=None):
+    """window: None, or (window_frames, overlap_frames): one more column, the windows of each channel.  loud: None,
+    or one row of LOUDNESS_COLUMNS values per file: five more columns, after every other."""
     with open(join(target_dir, "_enhanced.csv"), "w") as f:
-        f.write(",".join(CSV_COLUMNS + (("windows",) if window else ())) + "\n")
-        for path, n, ch, sr in files:
+        f.write(",".join(CSV_COLUMNS + (("windows",) if window else ()) + (LOUDNESS_COLUMNS if loud is not None else ()))
+                + "\n")
+        for i, (path, n, ch, sr) in enumerate(files):
             ro = sr if output_rate == "input" else audio.MODEL_RATE
             row = f"{os.path.basename(path)},{sr},{ch},{n / sr!r},{ro}"
             if window:
                 W, V, _ = longform.geometry(*window)
                 row += f",{len(longform.window_starts(audio.resampled_length(n, sr, audio.MODEL_RATE), W, V))}"
+            if loud is not None:
+                a, b, g, p, lim = (float(v) for v in loud[i])
+                row += f",{a!r},{b!r},{g!r},{p!r},{int(lim)}"
             f.write(row + "\n")
+
+
+def level_file(x, ro, noisy, sr, target, peak_db):
+    """One finished file through the loudness stage: x = its enhanced channels (float32 arrays at rate ro), noisy =
+    the file it came from ([channels, frames] at rate sr) -> (int16 [frames, channels] or [frames], the
+    LOUDNESS_COLUMNS values).  Both files are measured in one batch (one upload, one read-back); the gain applied
+    is 10^(gain_db / 20) of the gain_db reported, so the csv says exactly what was done."""
+    from . import loudness as ld, ops
+    dev = ops.current_device()
+    rows, lens, rates, groups = ld.batch_rows([(np.stack(x), ro), (noisy, sr)], dev)
+    lufs, pk = ld.measure_rows(rows, lens, rates, groups)
+    back = torch.cat([lufs, pk.to(torch.float64)]).cpu().numpy()
+    l_enh, l_in, p_enh = float(back[0]), float(back[1]), float(back[2])
+    want = l_in if target == "input" else target
+    if want == -np.inf:  # a silent noisy file sets no level
+        gain, limited = 1.0, False
+    else:
+        gain, limited = ld.plan_gain(l_enh, want, p_enh, peak_db)
+    gain_db = ld.db(gain)
+    gain = 10.0 ** (gain_db / 20.0)
+    ch, n = len(x), len(x[0])
+    q = ops.gain_to_pcm16(rows[:ch], torch.full((ch,), gain, device=dev, dtype=torch.float64), lengths=lens[:ch])
+    q = q[:, :n].cpu().numpy()
+    return (q[0] if ch == 1 else np.ascontiguousarray(q.T)), (l_in, l_enh, gain_db, ld.db(gain * p_enh), float(limited))
 
 
 def enhance_files(model, noisy_dir, target_dir, batch_size=32, max_frames=16384, output_rate="model", rank=0,
                   world=1, sampler_type="pc", predictor="reverse_diffusion", corrector="ald", corrector_steps=1,
                   snr=0.5, N=30, reverse_starting_point=1.0, force_N=0, atol=1e-5, rtol=1e-5,
                   timestep_type="linear", correct_stepsize=False, window_frames=None, overlap_frames=64,
-                  highband="drop", highband_floor_db=30.0, **enhance_kw):
+                  highband="drop", highband_floor_db=30.0, loudness="off", peak_db=-1.0, **enhance_kw):
     """-> the list_files() rows of every file (all ranks'); this rank's share is enhanced and written.
     window_frames / overlap_frames: ScoreModel.enhance_batch's (None: every channel is one network input), and so
-    are highband / highband_floor_db (anything but "drop" needs output_rate="input")."""
+    are highband / highband_floor_db (anything but "drop" needs output_rate="input").  loudness: "off", "input" or a
+    level in LUFS, peak_db: the ceiling on the 4x peak (module docstring)."""
     if output_rate not in ("model", "input"):
         raise ValueError(f"enhance_files: output_rate is 'model' or 'input', got {output_rate!r}")
     highband = resample.check_highband(highband, highband_floor_db, (), output_rate)
+    target = None
+    if loudness is not None and loudness != "off":  # off: the loudness layer is not even imported
+        from . import loudness as ld
+        target, peak_db = ld.parse_target(loudness), ld.check_ceiling(peak_db)
+    levels = []
     window = None
     if window_frames is not None:
         longform.geometry(window_frames, overlap_frames)
@@ -136,10 +187,23 @@ def enhance_files(model, noisy_dir, target_dir, batch_size=32, max_frames=16384,
             if all(v is not None for v in done[k]):
                 path, _, ch, sr = mine[k]
                 x = done.pop(k)
-                audio.write_wav(join(target_dir, os.path.basename(path)), x[0] if ch == 1 else np.stack(x, 1),
-                                sr if output_rate == "input" else audio.MODEL_RATE, bits=16)
+                ro = sr if output_rate == "input" else audio.MODEL_RATE
+                if target is None:
+                    audio.write_wav(join(target_dir, os.path.basename(path)), x[0] if ch == 1 else np.stack(x, 1), ro,
+                                    bits=16)
+                    continue
+                q, row = level_file(x, ro, loaded[k] if k in loaded else audio.load(path)[0], sr, target, peak_db)
+                levels.append((k, row))
+                audio.write_wav(join(target_dir, os.path.basename(path)), q, ro, bits=16)
+    loud = None
+    if target is not None:  # rank 0 writes every rank's rows
+        from . import ops
+        vals = np.zeros((len(mine), len(LOUDNESS_COLUMNS)), np.float64)
+        for k, row in levels:
+            vals[k] = row
+        loud = sdist.gather_metrics(vals, len(files), rank, world, ops.current_device()).cpu().numpy()
     if rank == 0:
-        write_csv(files, output_rate, target_dir, window)
+        write_csv(files, output_rate, target_dir, window, loud)
     return files
 
 
@@ -165,6 +229,11 @@ def parser():
                     help="keep that band at this fixed gain in dB (<= 0) instead")
     ap.add_argument("--highband_floor_db", type=float, default=30.0,
                     help="the most --highband follow attenuates the band, in dB")
+    ap.add_argument("--loudness", type=str, default="off",
+                    help="off (as before), input (the integrated loudness of the noisy file) or a target in LUFS, e.g. "
+                         "-23: one gain per file, applied on the device before the 16-bit conversion")
+    ap.add_argument("--peak_db", type=float, default=-1.0,
+                    help="ceiling in dB (<= 0) on the 4x-oversampled peak of a file written with --loudness")
     sampler_arguments(ap)
     return ap
 
@@ -182,7 +251,8 @@ def main(argv=None):
         torch.manual_seed(a.seed)
     enhance_files(model, a.noisy_dir, a.destination_folder, batch_size=a.batch_size, output_rate=a.output_rate,
                   rank=rank, world=world, window_frames=a.window_frames, overlap_frames=a.overlap_frames,
-                  highband=highband_argument(a), highband_floor_db=a.highband_floor_db, **sampler_kwargs(a))
+                  highband=highband_argument(a), highband_floor_db=a.highband_floor_db, loudness=a.loudness,
+                  peak_db=a.peak_db, **sampler_kwargs(a))
 
 
 if __name__ == "__main__":

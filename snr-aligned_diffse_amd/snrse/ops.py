@@ -969,6 +969,113 @@ def estoi(x, y, lengths=None, fs=16000, return_info=False):
     return (out, info) if return_info else out
 
 
+def _ragged_rows(what, x, lengths):
+    """The checks the loudness ops share -> (B, stride, host lengths int64); L_b = 0 is allowed."""
+    if not torch.is_tensor(x) or x.dim() != 2 or x.dtype != torch.float32:
+        raise TypeError(f"snrse: {what} takes a [B, L] float32 batch")
+    _dev(x)
+    B, L = x.shape
+    if B <= 0 or L <= 0:
+        raise ValueError(f"snrse: {what} needs a non-empty batch, got [{B}, {L}]")
+    if lengths is None:
+        return B, L, np.full(B, L, np.int64)
+    return B, L, _host_lengths(what, lengths.host if isinstance(lengths, Lengths) else lengths, B, 0, L)
+
+
+_KW_TABLES = {}  # (rates, groups, device) -> the device tables of loudness(), built once per batch layout
+
+
+def kweight_geometry():
+    """(chunk, block, group) of snrse_kweight_sums: samples per chunk, chunks per workgroup, chunks per scan group
+    -- the lengths at which its kernels change path."""
+    L = _lib.load()
+    return int(L.snrse_kweight_chunk()), int(L.snrse_kweight_block()), int(L.snrse_kweight_group())
+
+
+def loudness(x, lengths=None, rate=16000, groups=None, return_info=False):
+    """Integrated loudness (ITU-R BS.1770-4 as stated at snrse_kweight_sums in include/snrse.h; every channel has
+    weight 1) of a ragged batch: x [B, L] f32 on the device, row b valid on [0, L_b) (lengths None = whole rows,
+    L_b = 0 allowed), at `rate` Hz (a scalar, or one value per row) -> [G] f64 LUFS on the device, -inf for a file
+    without a block above the absolute gate.  groups: the file of each row (host integers 0, 0, 1, ..: rows of a
+    file adjacent, one rate per file; a file's channels are measured together), None = every row is a file.
+    return_info: also a dict: sums [B, Nmax] f64 (the sub-block energies), blocks / kept_abs / kept_rel [G] int32
+    and margin [G] f64 (the least distance in LU of a block from the gate it was compared with) on the device, nsub
+    and n100 [B] int64 on the host.  Seven launches, no read-back."""
+    B, L, host = _ragged_rows("loudness", x, lengths)
+    dev = x.device
+    rates = (int(rate),) * B if np.ndim(rate) == 0 else tuple(int(r) for r in np.asarray(rate).reshape(-1))
+    if len(rates) != B:
+        raise ValueError(f"snrse: loudness got {len(rates)} rates for {B} rows")
+    grp = tuple(range(B)) if groups is None else tuple(int(g) for g in np.asarray(groups).reshape(-1))
+    Cc, _, Sg = kweight_geometry()
+    key = (rates, grp, dev)
+    if key not in _KW_TABLES:
+        from . import loudness as _ld
+        if len(grp) != B or grp[0] != 0 or any(b - a not in (0, 1) for a, b in zip(grp, grp[1:])):
+            raise ValueError("snrse: loudness groups are one file index per row, 0, 0, 1, ..: ascending without gaps")
+        if any(ga == gb and ra != rb for ga, gb, ra, rb in zip(grp, grp[1:], rates, rates[1:])):
+            raise ValueError("snrse: the rows of a file share one rate")
+        n100 = np.array([_ld.n100(r) for r in rates], np.int64)
+        if (n100 < Cc).any():
+            raise ValueError(f"snrse: loudness needs sample rates of at least {10 * Cc - 5} Hz")
+        par = np.stack([_ld.kernel_params(r, Cc, Sg) for r in rates])
+        if len(_KW_TABLES) >= 64:
+            _KW_TABLES.clear()
+        _KW_TABLES[key] = (torch.from_numpy(par).to(dev), n100,
+                           torch.from_numpy(np.stack([n100, np.array(grp, np.int64)]).astype(np.int32)).to(dev))
+    par, n100, tab = _KW_TABLES[key]
+    G = grp[-1] + 1
+    nsub = host // n100
+    Nmax = max(int(nsub.max()), 1)
+    lt = torch.from_numpy(np.stack([host, nsub]).astype(np.int32)).to(dev)
+    nbytes = int(_lib.load().snrse_kweight_workspace(B, L))
+    work = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    sums = torch.empty(B, Nmax, device=dev, dtype=torch.float64)
+    _lib.call("snrse_kweight_sums", x.data_ptr(), lt[0].data_ptr(), B, L, par.data_ptr(), tab[0].data_ptr(),
+              work.data_ptr(), nbytes, sums.data_ptr(), Nmax, _stream())
+    out = torch.empty(G, device=dev, dtype=torch.float64)
+    counts = torch.empty(G, 3, device=dev, dtype=torch.int32)
+    margin = torch.empty(G, device=dev, dtype=torch.float64)
+    _lib.call("snrse_loudness_gate", sums.data_ptr(), Nmax, lt[1].data_ptr(), tab[0].data_ptr(), tab[1].data_ptr(), B,
+              G, out.data_ptr(), counts.data_ptr(), margin.data_ptr(), _stream())
+    if not return_info:
+        return out
+    return out, {"sums": sums, "blocks": counts[:, 0], "kept_abs": counts[:, 1], "kept_rel": counts[:, 2],
+                 "margin": margin, "nsub": nsub, "n100": n100}
+
+
+def peak_oversampled(x, lengths=None):
+    """[B, L] f32 on the device -> [B] f32: max |.| of each row oversampled 4x by resample_poly's default filter
+    (audio.resample_taps(4, 1), 81 taps), the bits of resample_poly(x, 4, 1, lengths)[0].abs() maximised over
+    [0, 4 L_b) without that signal being written; a NaN is skipped as absmax skips it.  A 4x peak, not the true
+    peak of BS.1770 Annex 2 (another filter).  One launch, no read-back."""
+    B, L, host = _ragged_rows("peak_oversampled", x, lengths)
+    from .audio import resample_taps
+    tp, half = cached_taps(resample_taps, 4, 1, x.device)
+    ln = torch.from_numpy(host.astype(np.int32)).to(x.device)
+    out = torch.empty(B, device=x.device, dtype=torch.float32)
+    _lib.call("snrse_peak_oversampled", x.data_ptr(), ln.data_ptr(), B, L, 4, half, tp.data_ptr(), out.data_ptr(),
+              _stream())
+    return out
+
+
+def gain_to_pcm16(x, gain, lengths=None, floats=False):
+    """x [B, L] f32 and gain [B] (f32 or f64), both on the device -> int16 [B, L] = clip(rint(fl32(fl32(gain_b) x)
+    32768), -32768, 32767), exactly what audio.write_wav(bits=16) makes of the float32 product, zero from L_b on;
+    floats: (int16, that product as f32 [B, L]).  One launch, no read-back."""
+    B, L, host = _ragged_rows("gain_to_pcm16", x, lengths)
+    if not torch.is_tensor(gain) or gain.dtype not in (torch.float32, torch.float64) or gain.shape != (B,):
+        raise TypeError(f"snrse: gain_to_pcm16 takes a [{B}] float32 or float64 gain")
+    _dev(gain)
+    gain = gain.to(torch.float64)
+    ln = torch.from_numpy(host.astype(np.int32)).to(x.device)
+    q = torch.empty(B, L, device=x.device, dtype=torch.int16)
+    f = torch.empty_like(x) if floats else None
+    _lib.call("snrse_gain_to_pcm16", x.data_ptr(), ln.data_ptr(), B, L, gain.data_ptr(), q.data_ptr(), _ptr(f),
+              _stream())
+    return (q, f) if floats else q
+
+
 def _snr_pair(what, clean, noise, lengths):
     """The checks the dataset-preparation ops share -> (B, stride, Lengths)."""
     if clean.dim() != 2 or clean.shape != noise.shape or clean.dtype != torch.float32 or noise.dtype != torch.float32:
